@@ -16,6 +16,17 @@ A "step" is one full quantized forward of one synthetic batch already resident i
 public call path: QModel.__call__ compiles the fused device plan on first use.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config vit|vit_int4|vit_tiny|mlp4096]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up (model, calibration, fused
+plan), W warm-up steps, K timed steps, then one JSON result line (`value`, `ms_per_step`).
+--dump-outputs DIR also writes what the last timed step returned to its caller, the logits
+of the batch, as DIR/logits.npy (float32; DIR/logits_rank<r>.npy per rank with N > 1 GPUs).
+The inputs are seeded, so two builds run with the same arguments can be compared output for
+output.  --full adds everything else to the line: the whole-batch parity check ("verified"),
+the per-kernel table and the roofline figures (one extra one-stream forward), the CPU
+baseline with its oracle check (--no-cpu-baseline leaves it out), and for the default config
+the secondary configs (int4, ViT-tiny, MLP-4096; --no-secondary leaves them out).
 
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) each process is one
 rank and WORLD_SIZE must equal --gpus.  Without it, `--gpus N` (N > 1) spawns the N
@@ -25,8 +36,8 @@ blob.py) reaches the other ranks as ONE RCCL broadcast over xGMI; each step ever
 rank runs its own batch and the logits are gathered to rank 0 over RCCL.
 numpy_quant/control.py (a TCP star, no PyTorch) is only the control plane.
 
-After the timed loop each rank checks its own output: all B rows must equal one batch-B
-run of the reference's node-by-node loop (QModel with keep_values), bit for bit
+With --full, after the timed loop each rank checks its own output: all B rows must equal
+one batch-B run of the reference's node-by-node loop (QModel with keep_values), bit for bit
 ("verified" in the JSON).
 """
 from __future__ import annotations
@@ -334,6 +345,28 @@ def verify_vit(model, qmodel, x, out_host) -> dict:
                        "reference's vectors by tests/test_gpu_models.py), every row"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: every rank's files together stay below this
+
+
+def dump_outputs(dirname: str, group, arrays: dict) -> None:
+    """--dump-outputs: the arrays the last timed step returned, as DIR/<name>.npy in float32
+    (float64 stays float64).  One GPU writes <name>.npy, N > 1 ranks <name>_rank<r>.npy each.
+    An array above this rank's share of DUMP_LIMIT_BYTES is cut to a fixed seeded sample of
+    its elements (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    limit = DUMP_LIMIT_BYTES // (group.world * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        if a.nbytes > limit:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, limit // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        suffix = f"_rank{group.rank}" if group.world > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+
 # ----------------------------------------------------------------------------- runs
 def run_vit(args, group):
     import numpy as np
@@ -369,6 +402,10 @@ def run_vit(args, group):
 
     ms_per_step, value, out = timed(step, args, group, args.batch * world)
     out_host = out.dev.to_host()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, group, {"logits": out_host})
+    if not args.full:
+        return plain_result(args, world, ms_per_step, value, bw, tiny, graph) if rank == 0 else None
     ver = verify_vit(model, qmodel, x, out_host)
     nbad = group.max(float(len(ver["mismatched_images"])))
     ver["verified"] = nbad == 0
@@ -382,16 +419,7 @@ def run_vit(args, group):
     mm_tops = (proj["ops"] + proj["attn_ops"]) / ((proj["ms"] + proj["attn_ms"]) * 1e-3) / 1e12
     step_tops = proj["int8_ops"] / (ms_per_step * 1e-3) / 1e12 / world
     traffic, traffic_by = traffic_from_profiles(tiny) if bw == 8 else (None, None)
-    res = result_head(args, world, ms_per_step, value, f"int{bw}")
-    arch = ("ViT-Ti/16-224: the graph re-dimensioned to width 192, 3 heads, MLP 768 (onnx_proto.redimension)"
-            if tiny else "ViT-Base/16-224")
-    res["config"] = {"workload": f"vit_image_classifier (reference models/vit graph, {arch}), "
-                                 f"QModel.__call__ (fused plan), int{bw}, batch {args.batch}/GPU",
-                     "model": f"vit_image_classifier_no_weights.onnx ({arch})",
-                     "global_batch": args.batch * world, "seq_len": 197,
-                     "parallelism": f"replicas x{world}",
-                     "executor": "fused plan" + (", hipGraph replay" if graph else "") +
-                                 (", int4 nibble-packed weights" if bw <= 4 else "")}
+    res = plain_result(args, world, ms_per_step, value, bw, tiny, graph)
     res["matmul_tops"] = round(achieved, 2)
     res["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(INT8_PEAK_TOPS, 1),
                        "unit": "TOPS", "frac": round(achieved / INT8_PEAK_TOPS, 4),
@@ -427,6 +455,21 @@ def run_vit(args, group):
     return res
 
 
+def plain_result(args, world, ms_per_step, value, bw, tiny, graph) -> dict:
+    """The ViT result line of a plain run: the headline figures and the workload."""
+    res = result_head(args, world, ms_per_step, value, f"int{bw}")
+    arch = ("ViT-Ti/16-224: the graph re-dimensioned to width 192, 3 heads, MLP 768 (onnx_proto.redimension)"
+            if tiny else "ViT-Base/16-224")
+    res["config"] = {"workload": f"vit_image_classifier (reference models/vit graph, {arch}), "
+                                 f"QModel.__call__ (fused plan), int{bw}, batch {args.batch}/GPU",
+                     "model": f"vit_image_classifier_no_weights.onnx ({arch})",
+                     "global_batch": args.batch * world, "seq_len": 197,
+                     "parallelism": f"replicas x{world}",
+                     "executor": "fused plan" + (", hipGraph replay" if graph else "") +
+                                 (", int4 nibble-packed weights" if bw <= 4 else "")}
+    return res
+
+
 def run_mlp(args, group):
     import numpy as np
     from numpy_quant.model import Model
@@ -438,22 +481,26 @@ def run_mlp(args, group):
     x = np.random.default_rng(4096 + rank).uniform(-1.2, 1.2, size=(B, 2)).astype(np.float32)
     qmodel = Model.from_onnx(MLP_FILE).quantize([X], bit_width=bw)
     x_dev = FTensor(x)
-    ref = qmodel([x])[0]
+    ref = qmodel([x])[0] if args.full else None  # the node loop, before the plan is captured (as ever)
     graph = qmodel.graph([x_dev])
 
     def step():
         return graph.run_device([x_dev])[0]
 
-    steps = args.steps
     ms_per_step, value, out = timed(step, args, group, B * world)
-    ok = bool(np.array_equal(out.dev.to_host(), ref))
-    nbad = group.max(0.0 if ok else 1.0)
-    if rank != 0:
-        return None
+    out_host = out.dev.to_host()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, group, {"logits": out_host})
     res = result_head(args, world, ms_per_step, value, f"int{bw}")
     res["config"] = {"workload": f"mlp.onnx (reference models/mlp.onnx, 2-5-2 MLP), QModel.__call__ replayed as one "
                                  f"hipGraph, int{bw}, batch {B}/GPU", "model": "mlp.onnx",
                      "global_batch": B * world, "seq_len": 1, "parallelism": f"replicas x{world}"}
+    if not args.full:
+        return res if rank == 0 else None
+    ok = bool(np.array_equal(out_host, ref))
+    nbad = group.max(0.0 if ok else 1.0)
+    if rank != 0:
+        return None
     # bytes the forward must move: x f32 in, 4 quantize / requantize / dequantize passes
     byts = B * (2 * 4 + 2 * 1 + 5 * 4 + 5 * 1 + 5 * 4 + 5 * 1 + 2 * 4 + 2 * 1 + 2 * 4 + 2 * 4)
     gbs = byts / (ms_per_step * 1e-3) / 1e9
@@ -500,16 +547,23 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--bit-width", type=int, default=8)
     ap.add_argument("--config", choices=("vit", "vit_int4", "vit_tiny", "mlp4096"), default="vit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the logits) as DIR/logits.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: the whole-batch parity check, the per-kernel table and "
+                         "roofline, the CPU baseline with its oracle check, the secondary configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-baseline", choices=("full", "layer"), default="full",
                     help="full: the oracle's whole ViT forward on one image (measured); layer: one layer x12")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the int4 / ViT-tiny / MLP-4096 lines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the int4 / ViT-tiny / MLP-4096 lines")
     ap.add_argument("--graph", type=int, default=1,
                     help="1 (default): replay the ViT forward as one captured hipGraph (QModel.graph: the fused "
                          "plan's launches of both batch parts, captured once); 0: issue them from Python every step "
                          "(+0.5 .. 0.9 %% with the graph, profiles/r05_graph_ab.txt)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)  # launcher test: no GPU
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -540,7 +594,7 @@ def main(argv=None):
     _lib.ensure_init(group.local_rank)
     try:
         res = run_mlp(args, group) if args.config == "mlp4096" else run_vit(args, group)
-        if res is not None and args.config == "vit" and world == 1 and not args.no_secondary:
+        if res is not None and args.full and args.config == "vit" and world == 1 and not args.no_secondary:
             res["secondary"] = run_secondary(args, group)
         if res is not None:
             print(json.dumps(res), flush=True)
@@ -558,7 +612,7 @@ def run_secondary(args, group) -> dict:
     for cfg in ("vit_int4", "vit_tiny", "mlp4096"):
         sub = copy.copy(args)
         sub.config, sub.steps, sub.warmup, sub.no_cpu_baseline = cfg, min(args.steps, 10), min(args.warmup, 2), True
-        sub.graph = args.graph
+        sub.graph, sub.dump_outputs = args.graph, None
         t0 = time.time()
         try:
             r = run_mlp(sub, group) if cfg == "mlp4096" else run_vit(sub, group)

@@ -10,16 +10,17 @@
 #   AB_BENCH="--steps 20 ..."    extra bench.py arguments (default: --steps 20)
 #   AB_MICRO="pg|attn|ln"        tools/pg_micro.py / attn_micro.py / ln_micro.py afterwards
 #                                (their PGM_* / AM_* variables pass through)
-#   OUT=tag                      results: gpurun_out/<tag>_*.json, <tag>_ab.txt
+#   OUT=tag                      results: $RESULTS_DIR/<tag>_*.json, <tag>_ab.txt
 # Every GPU step runs under its own time limit; the first failure ends the call.
 set -u
-mkdir -p gpurun_out
+R=${RESULTS_DIR:-results}  # where this script leaves its logs and result files
+mkdir -p $R
 export TMPDIR=/tmp
 OUT=${OUT:-ab}
-fail() { echo "FAILED: $1 rc=$2" >> gpurun_out/${OUT}_ab.txt; exit $2; }
+fail() { echo "FAILED: $1 rc=$2" >> $R/${OUT}_ab.txt; exit $2; }
 if [ -n "${AB_TESTS:-}" ]; then
   timeout -k 10 600 python -u -m pytest ${AB_TESTS} -x -q --timeout 300 --timeout-method thread \
-    > gpurun_out/${OUT}_tests.log 2>&1 || fail pytest $?
+    > $R/${OUT}_tests.log 2>&1 || fail pytest $?
 fi
 LIB=numpy-quant_amd/numpy_quant/libnqk.so
 cp $LIB /tmp/libnqk_main.so
@@ -36,16 +37,16 @@ for rep in $(seq 1 ${AB_REPS:-2}); do
       name=$v
       if [ "$v" = "main" ]; then cp /tmp/libnqk_main.so $LIB; else cp tools/diag/libnqk_$v.so $LIB; fi
     fi
-    env ${envs//,/ } timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-secondary ${AB_BENCH:---steps 20} \
-      > gpurun_out/${OUT}_${name}_$rep.json 2> gpurun_out/${OUT}_${name}_$rep.err || fail "bench $name" $?
-    python3 -c "import json;d=json.load(open('gpurun_out/${OUT}_${name}_$rep.json'));print('$name', d['value'], d['ms_per_step'], d['verified'], d['roofline']['frac'], {k:v['avg_us'] for k,v in d['kernels'].items()})" \
-      >> gpurun_out/${OUT}_ab.txt
+    env ${envs//,/ } timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-secondary ${AB_BENCH:---steps 20} \
+      > $R/${OUT}_${name}_$rep.json 2> $R/${OUT}_${name}_$rep.err || fail "bench $name" $?
+    python3 -c "import json;d=json.load(open('$R/${OUT}_${name}_$rep.json'));print('$name', d['value'], d['ms_per_step'], d['verified'], d['roofline']['frac'], {k:v['avg_us'] for k,v in d['kernels'].items()})" \
+      >> $R/${OUT}_ab.txt
   done
 done
 cp /tmp/libnqk_main.so $LIB
 case "${AB_MICRO:-}" in
-  pg) timeout -k 10 300 python -u tools/pg_micro.py > gpurun_out/${OUT}_pg_micro.txt 2>&1 || fail pg_micro $? ;;
-  attn) timeout -k 10 300 python -u tools/attn_micro.py > gpurun_out/${OUT}_attn_micro.txt 2>&1 || fail attn_micro $? ;;
-  ln) timeout -k 10 300 python -u tools/ln_micro.py > gpurun_out/${OUT}_ln_micro.txt 2>&1 || fail ln_micro $? ;;
+  pg) timeout -k 10 300 python -u tools/pg_micro.py > $R/${OUT}_pg_micro.txt 2>&1 || fail pg_micro $? ;;
+  attn) timeout -k 10 300 python -u tools/attn_micro.py > $R/${OUT}_attn_micro.txt 2>&1 || fail attn_micro $? ;;
+  ln) timeout -k 10 300 python -u tools/ln_micro.py > $R/${OUT}_ln_micro.txt 2>&1 || fail ln_micro $? ;;
 esac
-echo done >> gpurun_out/${OUT}_ab.txt
+echo done >> $R/${OUT}_ab.txt
