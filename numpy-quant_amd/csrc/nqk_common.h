@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/nqk.h"
+#include "nqk_xcd.h"
 
 namespace nqk {
 
@@ -11,6 +12,9 @@ hipStream_t stream();                      // the library stream of the current 
 int fail(const std::string& msg);          // record an error message, return -1
 int check(hipError_t e, const char* what); // 0 or fail()
 inline int launch_status(const char* what) { return check(hipGetLastError(), what); }
+// XCDs of the current device (hipDeviceAttributeNumberOfXccs; 8 on MI355X): the band count of the
+// XCD-aware tile orders (nqk_xcd.h).  NQK_XCDS=1..16 overrides it (read on every call: tests)
+int xcd_count();
 
 // 64-bit grid-stride helpers
 constexpr int kThreads = 256;

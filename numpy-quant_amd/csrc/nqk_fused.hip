@@ -421,8 +421,7 @@ k_qgemm_epi(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
   int wg = blockIdx.x;
   const int xc = e.xcds;
   if (nwg >= xc && xc > 0) {
-    const int q = nwg / xc, r = nwg % xc, x = wg % xc;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / xc;
+    wg = xcd_remap<int>(wg, nwg, xc);
   }
   const int tm = wg / tiles_n, tn = wg % tiles_n;
   const int m0 = tm * FBM, n0 = tn * FBN;
@@ -819,8 +818,7 @@ __device__ __forceinline__ void proj_epilogue(int8_t* lds, v16i (&acc)[4][2], co
 __device__ __forceinline__ int xcd_tile(int nwg, int xc) {
   int wg = blockIdx.x;
   if (NQK_TILE_ORDER != 1 && nwg >= xc && xc > 0) {
-    const int q = nwg / xc, r = nwg % xc, x = wg % xc;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / xc;
+    wg = xcd_remap<int>(wg, nwg, xc);
   }
   return wg;
 }
@@ -1505,6 +1503,9 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
       const double rs_out = g3 == 0 ? e.rs_out[0] : (g3 == 1 ? e.rs_out[1] : e.rs_out[2]);
       const double zp = g3 == 0 ? e.zp_out[0] : (g3 == 1 ? e.zp_out[1] : e.zp_out[2]);
       void* op = g3 == 0 ? e.out[0] : (g3 == 1 ? e.out[1] : e.out[2]);
+      // QKV: M * group_cols bytes is the end of the head-split output only for whole images; with
+      // M % tokens != 0 this range cuts the last image's later heads and admits rows past M of the
+      // earlier ones, so the host gives k_proj the QKV epilogue only when M % tokens == 0
       const rsrc_t out = make_rsrc(op, (uint32_t)(EPI == EPI_QKV ? (uint64_t)M * e.group_cols : (uint64_t)M * N));
       // batches of NG register groups (QKV: a whole MFMA tile, 16 values; GELU, whose
       // fast path holds more temporaries: half a tile), j-major: the column constants of
@@ -2256,12 +2257,11 @@ template <int EPI, bool F32X, int NK, bool B4>
 static void launch_proj(const int8_t* a, const int8_t* bp, int64_t M, int64_t N, int64_t lda, const Epi& e) {
   const int tn = (int)(N / GBN), nt = (int)((M + 255) / 256) * tn;
   // workgroups (one per CU): all CUs, or NQK_PROJ_CUS of them (diagnostic: a persistent
-  // GEMM of one stream's half batch leaving CUs to the other stream)
-  static const int cus = [] {
-    const char* v = getenv("NQK_PROJ_CUS");
-    const int n = v ? atoi(v) : 0;
-    return n > 0 && n < num_cus() ? n : num_cus();
-  }();
+  // GEMM of one stream's half batch leaving CUs to the other stream); read on every call, so
+  // that a test can give few workgroups many tiles each
+  const char* cv = getenv("NQK_PROJ_CUS");
+  const int cn = cv ? atoi(cv) : 0;
+  const int cus = cn > 0 && cn < num_cus() ? cn : num_cus();
   const int grid = nt < cus ? nt : cus;
   const size_t shm = p2_lds(EPI, B4);
   hipLaunchKernelGGL((k_proj<EPI, F32X, NK, B4>), dim3(grid), dim3(512), shm, stream(), a, bp, (int)M, (int)N, (int)lda,
@@ -2317,16 +2317,7 @@ static Epi make_epi(const nqk_epilogue* p) {
   e.colterm = p->colterm;
   e.lof = (float)e.lo;
   e.hif = (float)e.hi;
-  e.xcds = [] {
-    static int n = 0;
-    if (n == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess ||
-          n <= 0)
-        n = 8;
-    }
-    return n;
-  }();
+  e.xcds = xcd_count();
   e.ln_g = p->ln_gamma;
   e.ln_b = p->ln_beta;
   e.ln_out = p->ln_out;
@@ -2447,7 +2438,10 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
                             ((epi == EPI_RESID && !(params->b_packed == 2 && K == 768) && getenv("NQK_PROJ_RESID")) ||
                              (f32x && K == 768 &&
                               ((epi == EPI_GELU && getenv("NQK_PROJ_GELU")) ||
-                               (epi == EPI_QKV && params->tokens >= 64 && params->hdim == 64 && params->group_cols % 128 == 0 &&
+                               // (whole images only: k_proj bounds its head-split stores by M * group_cols bytes, which
+                               // cuts the last image's later heads and lets rows past M through when M % tokens != 0)
+                               (epi == EPI_QKV && params->tokens >= 64 && M % params->tokens == 0 && params->hdim == 64 &&
+                                params->group_cols % 128 == 0 &&
                                 (double)M * params->heads * params->hdim < 2147483647.0))));
     if (proj_shape) {
       const bool b4 = params->b_packed == 2;

@@ -413,16 +413,7 @@ k_sgemm_mfma(const float* __restrict__ A, const float* __restrict__ B, float* __
 // writes its 8 k values of each k-tile as two ds_write_b128.
 // XCDs of the device (hipDeviceAttributeNumberOfXccs; 8 on MI355X): the round-robin unit of the
 // XCD-aware tile orders (not a constant)
-static int num_xcds() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess ||
-        n <= 0)
-      n = 8;
-  }
-  return n;
-}
+static int num_xcds() { return xcd_count(); }
 constexpr int EQ_ROW = 20;  // floats per LDS operand row (16 + 4 padding)
 #ifndef NQK_EMBED_PXD
 #define NQK_EMBED_PXD 1
@@ -448,8 +439,7 @@ k_embed_q(const int8_t* __restrict__ q, const float* __restrict__ wt, float* __r
   int64_t tm = blockIdx.y, tn = blockIdx.x;
   if (ee.xcd) {
     const int64_t gx = gridDim.x, T = gx * gridDim.y, b = (int64_t)blockIdx.y * gx + blockIdx.x;
-    const int64_t XC = ee.xcd, x = b % XC, q8 = T / XC, r8 = T % XC;
-    const int64_t tile = x * q8 + (x < r8 ? x : r8) + b / 8;
+    const int64_t tile = xcd_remap<int64_t>(b, T, ee.xcd);
     tm = tile / gx;
     tn = tile - tm * gx;
   }
@@ -638,8 +628,7 @@ k_embed_q16(const int8_t* __restrict__ q, const float* __restrict__ wt, float* _
   int64_t tm = blockIdx.y, tn = blockIdx.x;
   if (ee.xcd) {  // XCD-aware tile order, as k_embed_q
     const int64_t gx = gridDim.x, T = gx * gridDim.y, b = (int64_t)blockIdx.y * gx + blockIdx.x;
-    const int64_t XC = ee.xcd, x = b % XC, q8 = T / XC, r8 = T % XC;
-    const int64_t tile = x * q8 + (x < r8 ? x : r8) + b / XC;
+    const int64_t tile = xcd_remap<int64_t>(b, T, ee.xcd);
     tm = tile / gx;
     tn = tile - tm * gx;
   }

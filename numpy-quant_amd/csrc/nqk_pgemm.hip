@@ -83,16 +83,7 @@ static int pg_num_cus() {
   return n;
 }
 
-static int pg_num_xcds() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess ||
-        n <= 0)
-      n = 8;
-  }
-  return n;
-}
+static int pg_num_xcds() { return xcd_count(); }
 
 // Launches k_pg for one projection GEMM when it takes the case; returns the kernel id for
 // nqk_qgemm_last_kernel (4 k_pg, 6 k_pg with the GELU table) if launched, 0 if the caller

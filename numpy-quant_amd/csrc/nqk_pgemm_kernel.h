@@ -423,11 +423,8 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   // tiles: the workgroups with blockIdx % 8 == x (one XCD under round-robin placement)
   // walk the band [lo, hi) of tile ids, every nx-th tile from lo + jx; tile ids are
   // row-panel major, so the tiles in flight on an XCD share A row panels in its L2.
-  const int G = gridDim.x, X = G < e.xcds ? G : e.xcds, x = blockIdx.x % X;
-  const int nx = (G - x + X - 1) / X;
-  const int lo = (int)((int64_t)ntiles * x / X), hi = (int)((int64_t)ntiles * (x + 1) / X);
-  const int first = lo + (int)(blockIdx.x / X);
-  const int iters = first < hi ? (hi - first + nx - 1) / nx : 0;
+  const XcdWalk xw = xcd_walk((int)blockIdx.x, (int)gridDim.x, ntiles, e.xcds);  // nqk_xcd.h
+  const int G = gridDim.x, first = xw.first, nx = xw.step, iters = xw.iters;
   if (iters == 0) return;
   auto tile_at = [&](int it) { return first + (it < iters ? it : iters - 1) * nx; };
 

@@ -2,6 +2,8 @@
 // timers and hipGraph capture (include/nqk.h "runtime").
 #include "nqk_common.h"
 
+#include <stdlib.h>
+
 #include <mutex>
 #include <string>
 
@@ -27,6 +29,20 @@ int check(hipError_t e, const char* what) {
 hipStream_t stream() {
   if (g_device < 0) nqk_init(0);
   return g_cur ? g_side[g_device][g_cur - 1] : g_streams[g_device];
+}
+int xcd_count() {
+  if (const char* v = getenv("NQK_XCDS")) {
+    const int o = atoi(v);
+    if (o >= 1 && o <= 16) return o;
+  }
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess ||
+        n <= 0)
+      n = 8;
+  }
+  return n;
 }
 }  // namespace nqk
 

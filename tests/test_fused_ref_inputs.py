@@ -1,0 +1,53 @@
+"""The input conditions of tests/test_gpu_fused_reference.py, checked on the reference alone (no
+GPU): the builders of tests/_fused_cases.py assert them, this test runs the builders and states
+the figures found.
+
+* accumulator extremes: max |acc - col zpa| over the extreme rows EQUALS the bound of the
+  f32-exactness proof (16 515 072 / 16 773 120 just below 2^24; 16 809 984, 26 345 472,
+  16 902 144 above), odd and even values within 5 % of it, and 0 .. 34 % of the extreme rows'
+  outputs equal lo or hi;
+* exact ties: 0.78 % (K = 192) and 0.69 % (K = 768) of the QKV elements, 0.75 % of the PV elements
+  are unclipped exact ties, with even and odd floors;
+* fused LayerNorm: under 28 % of the outputs clipped at every bit width and zero point;
+* attention: flat rows (all arguments 0), peaked rows (the runner-up 216.75 behind), and at
+  T >= 197 rows with 2 x T arguments within 2 above and 3 x T within 2 below -86.5."""
+import pytest
+
+import _fused_cases as F
+
+
+@pytest.mark.parametrize("case", [c for c, _ in F.EXTREME_CASES], ids=lambda c: "-".join(map(str, c)))
+def test_extreme_rows_reach_the_bound(case):
+    st = F.gemm_case(case)["stats"]
+    print(case, st)
+    assert st["vmax"] == st["bound"] and st["parities"] == [0, 1]
+    assert st["below"] == (case.zpa in (40, 2))
+    assert (st["bound"] < 1 << 24) == st["below"]
+    assert case.epi == "resid" or st["clipped"] < 0.5
+
+
+@pytest.mark.parametrize("case", [c for c, _ in F.TIES_CASES], ids=lambda c: "-".join(map(str, c)))
+def test_ties_occur(case):
+    st = F.gemm_case(case)["stats"]
+    print(case, st)
+    assert st["tie_share"] >= 0.005 and st["even"] > 0 and st["odd"] > 0
+    st = F.pv_ties_case()["stats"]
+    print("pv", st)
+    assert st["tie_share"] >= 0.005 and st["even"] > 0 and st["odd"] > 0
+
+
+@pytest.mark.parametrize("case", [c for c, _ in F.LN_CASES], ids=lambda c: "-".join(map(str, c)))
+def test_layernorm_outputs_not_all_clipped(case):
+    st = F.gemm_case(case)["stats"]
+    print(case, st)
+    assert st["clipped"] < 0.5
+
+
+@pytest.mark.parametrize("case", F.ATTN_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_softmax_rows_have_the_stated_kinds(case):
+    st = F.attn_case(case)["stats"]
+    print(case, st)
+    if case.T >= 16 and case.bw == 8:
+        assert st["peak_gap"] > 104
+    if case.T >= 197:
+        assert st["straddle"][0] > 0 and st["straddle"][1] > 0

@@ -19,13 +19,8 @@ SQRT2_F32 = float(np.float32(1.4142135381698608))
 
 
 def _build(s_out, zp, bw=8):
-    from numpy_quant import _lib
-    from numpy_quant.device import DeviceArray
-    lut = DeviceArray((8192,), np.uint8)
-    k = (ctypes.c_float * 5)()
-    n = ctypes.c_int32(-1)
-    _lib.call("nqk_gelu_lut_build", float(np.float32(s_out)), int(zp), bw, SQRT2_F32, 1.0, 0.5, lut.vp, k, ctypes.byref(n))
-    return lut, k, n.value
+    from _fused_gpu import build_gelu_lut
+    return build_gelu_lut(s_out, zp, bw)
 
 
 def _check(lut, k, n, s_out, zp, bw=8):
@@ -92,45 +87,24 @@ def test_gelu_table_refuses_other_chains():
 
 
 def _gelu_gemm(M, N, K, s_out, zp, seed, table, monkeypatch, wm=0, wbits=8):
-    from numpy_quant import _lib
-    from numpy_quant.device import DeviceArray
-    from numpy_quant.plan import EPI_GELU, _gemm, _pack_b, _pack_pg
+    from _fused_gpu import fused_gemm
     rng = np.random.default_rng(seed)
-    a = DeviceArray.from_host(rng.integers(-128, 128, size=(M, K), dtype=np.int8))
+    a_h = rng.integers(-128, 128, size=(M, K), dtype=np.int8)
     bt_h = rng.integers(-24, 25, size=(N, K), dtype=np.int8) if wbits == 8 else rng.integers(-8, 8, size=(N, K), dtype=np.int8)
-    bt = DeviceArray.from_host(bt_h)
-    col_h = bt_h.astype(np.int64).sum(axis=1)
-    col = DeviceArray.from_host(col_h)
-    bias = DeviceArray.from_host((0.05 * rng.standard_normal(N)).astype(np.float32))
-    packed, kind = _pack_b(bt, wbits)
-    pg = _pack_pg(bt, wbits, 0, nibbles=kind == 2)
-    zpa = -5
-    colterm = DeviceArray.from_host((col_h * zpa).astype(np.int32))
+    bias_h = (0.05 * rng.standard_normal(N)).astype(np.float32)
     for v in ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_NO_GLUT", "NQK_PG_WM"):
         monkeypatch.delenv(v, raising=False)
     if wm:
         monkeypatch.setenv("NQK_PG_WM", str(wm))
-    e = _lib.Epilogue()
     obits = 8 if wbits == 8 else 4  # int4 weights come with 4-bit outputs (the int4 model)
-    e.zp_flags, e.bit_width = _lib.ZP_COL, obits
-    e.zpa, e.col, e.col_absmax = zpa, col.ptr, int(np.abs(col_h).max())
-    e.bias, e.b_packed, e.colterm, e.bt_pg = bias.ptr, kind, colterm.ptr, pg.ptr
-    e.group_cols = 1 << 30
-    out = DeviceArray((M, N), np.int8)
-    out.fill_zero()
-    e.s_acc[0], e.s_out[0], e.zp_out[0], e.out[0] = float(np.float32(1.3e-4)), float(np.float32(s_out)), zp, out.ptr
-    e.div, e.add1, e.mul2 = SQRT2_F32, 1.0, 0.5
-    keep = None
+    lut = None
     if table:
-        lut, k, n = _build(s_out, zp, obits)
-        assert n > 0
-        e.gelu_lut, e.lut_n = lut.ptr, n
-        for j in range(5):
-            e.lut_k[j] = k[j]
-        keep = lut
-    _gemm(EPI_GELU, a, packed, 1, M, N, K, K, K, None, 0, 0, e)
-    del keep
-    return _lib.load().nqk_qgemm_last_kernel(), out.to_host()
+        lut = _build(s_out, zp, obits)
+        assert lut[2] > 0
+    kernel, outs, _ = fused_gemm("gelu", a_h, bt_h, zpa=-5, bias_h=bias_h, s_acc=[np.float32(1.3e-4)],
+                                 s_out=[np.float32(s_out)], zp_out=[zp], bw=obits, weights="pack" if wbits == 8 else "pack4",
+                                 pg="pg" if wbits == 8 else "pg4", lut=lut)
+    return kernel, outs[0]
 
 
 @pytest.mark.parametrize("M,N,K,s_out,zp", [

@@ -18,24 +18,15 @@ def _last_kernel():
 
 
 def _run(epi_name, M, N, K, s_out_scale, use_pg, no_f32x, monkeypatch, seed, kernel=2, bw=8, l1=False, proj=False):
-    from numpy_quant import _lib
-    from numpy_quant.device import DeviceArray
-    from numpy_quant.plan import EPI_GELU, EPI_QKV, EPI_RESID, _gemm, _pack_b, _pack_pg
-    epi = {"qkv": EPI_QKV, "resid": EPI_RESID, "gelu": EPI_GELU}[epi_name]
+    from _fused_gpu import fused_gemm
     rng = np.random.default_rng(seed)
-    a = DeviceArray.from_host(rng.integers(-128, 128, size=(M, K), dtype=np.int8))
+    a_h = rng.integers(-128, 128, size=(M, K), dtype=np.int8)
     lim = {8: 24, 6: 32, 4: 8}[bw]  # weights inside the bit width's range
     bt_h = rng.integers(-lim, lim + (1 if bw == 8 else 0), size=(N, K), dtype=np.int8)
-    bt = DeviceArray.from_host(bt_h)
     col_h = bt_h.astype(np.int64).sum(axis=1)
-    col = DeviceArray.from_host(col_h)
-    bias = DeviceArray.from_host((0.05 * rng.standard_normal(N)).astype(np.float32))
-    resid = DeviceArray.from_host(rng.standard_normal((M, N)).astype(np.float32))
-    packed, kind = _pack_b(bt, bw)
-    pg = _pack_pg(bt, bw, 1 if epi == EPI_RESID else 0, nibbles=kind == 2)
-    assert pg is not None
+    bias_h = (0.05 * rng.standard_normal(N)).astype(np.float32)
+    resid_h = rng.standard_normal((M, N)).astype(np.float32)
     zpa = -5
-    colterm = DeviceArray.from_host((col_h * zpa).astype(np.int32))
     for k in ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.delenv("NQK_PROJ_RESID", raising=False)
@@ -46,36 +37,22 @@ def _run(epi_name, M, N, K, s_out_scale, use_pg, no_f32x, monkeypatch, seed, ker
     monkeypatch.setenv("NQK_PG_WM", str(kernel))
     if no_f32x:
         monkeypatch.setenv("NQK_NO_F32X", "1")
-    e = _lib.Epilogue()
-    e.zp_flags, e.bit_width = _lib.ZP_COL, bw
-    e.zpa, e.col, e.col_absmax = zpa, col.ptr, int(np.abs(col_h).max())
-    e.bias, e.b_packed, e.colterm = bias.ptr, kind, colterm.ptr
-    if l1:  # the weights' largest column L1 norm: the tighter |acc| bound of the f32 proof
-        e.col_l1max = int(np.abs(bt_h.astype(np.int64)).sum(axis=1).max())
-    e.bt_pg = pg.ptr if use_pg else None
     sa = 1.3e-4
-    if epi == EPI_QKV:
-        T, H, Dh = 197, N // 3 // 64, 64
-        e.group_cols, e.tokens, e.heads, e.hdim = N // 3, T, H, Dh
-        bufs = [DeviceArray((-(-M // T) * H * T, Dh), np.int8) for _ in range(3)]
-        for g in range(3):
-            e.s_acc[g] = float(np.float32(sa * (g + 1)))
-            e.s_out[g] = (0.0021, 0.0173, 0.05)[g] * s_out_scale
-            e.zp_out[g], e.out[g] = (3, -140, 0)[g] if bw == 8 else (3, -20, 0)[g], bufs[g].ptr
-    elif epi == EPI_RESID:
-        e.group_cols = 1 << 30
-        bufs = [DeviceArray((M, N), np.float32)]
-        e.s_acc[0], e.out[0], e.resid = float(np.float32(sa * 2)), bufs[0].ptr, resid.ptr
+    if epi_name == "qkv":
+        s_acc = [np.float32(sa * (g + 1)) for g in range(3)]
+        s_out = [(0.0021, 0.0173, 0.05)[g] * s_out_scale for g in range(3)]
+        zp_out = (3, -140, 0) if bw == 8 else (3, -20, 0)
+    elif epi_name == "resid":
+        s_acc, s_out, zp_out = [np.float32(sa * 2)], (1.0, 1.0, 1.0), (0, 0, 0)
     else:
-        e.group_cols = 1 << 30
-        bufs = [DeviceArray((M, N), np.int8)]
-        e.s_acc[0], e.s_out[0], e.zp_out[0], e.out[0] = float(np.float32(sa)), 0.0027 * s_out_scale, -9, bufs[0].ptr
-        e.div, e.add1, e.mul2 = float(np.float32(1.4142135381698608)), 1.0, 0.5
-    for b in bufs:
-        b.fill_zero()
-    _gemm(epi, a, packed, 1, M, N, K, K, K, None, 0, 0, e)
-    host = dict(a=a.to_host(), bt=bt_h, colterm=col_h * zpa, bias=bias.to_host(), resid=resid.to_host(), e=e)
-    return _last_kernel(), [b.to_host() for b in bufs], host
+        s_acc, s_out, zp_out = [np.float32(sa)], [0.0027 * s_out_scale], [-9]
+    # the weights' largest column L1 norm (l1): the tighter |acc| bound of the f32 proof
+    kernel_id, outs, e = fused_gemm(epi_name, a_h, bt_h, zpa=zpa, bias_h=bias_h, resid_h=resid_h, s_acc=s_acc, s_out=s_out,
+                                    zp_out=zp_out, bw=bw, weights="pack4" if bw <= 4 else "pack",
+                                    pg="pg4" if bw <= 4 else "pg", use_pg=use_pg,
+                                    col_l1max=int(np.abs(bt_h.astype(np.int64)).sum(axis=1).max()) if l1 else 0)
+    host = dict(a=a_h, bt=bt_h, colterm=col_h * zpa, bias=bias_h, resid=resid_h, e=e)
+    return kernel_id, outs, host
 
 
 def _numpy_ref(epi_name, M, N, K, host):
