@@ -81,6 +81,18 @@ int nqk_event_destroy(void* event);
 /* the current stream waits for the work an event recorded (cross-stream ordering of the fused
  * plan's batch parts: NQK_STREAM_LAG) */
 int nqk_event_wait(void* event);
+/* Pinned (page-locked) host memory and the asynchronous upload from it (QModel.classify_stream:
+ * batch k + 1 travels while batch k computes).  nqk_upload_async enqueues the copy on the
+ * library's copy stream (created on first use; not the library stream, not a side stream 1..3),
+ * records done_event there (may be NULL) and returns without waiting: a consumer orders itself
+ * behind the copy with nqk_event_wait(done_event).  nqk_upload_wait_for makes the copy stream wait
+ * for an event, so that a later upload does not overwrite a device buffer before the kernel that
+ * reads it (which recorded the event with nqk_event_record) is done.  src_pinned must stay valid
+ * and unchanged until the copy has run.  nqk_sync waits for the copy stream too. */
+int nqk_host_alloc(void** ptr, size_t bytes);
+int nqk_host_free(void* ptr);
+int nqk_upload_async(void* dst, const void* src_pinned, size_t bytes, void* done_event);
+int nqk_upload_wait_for(void* event);
 /* hipGraph capture of everything issued between begin and end (relaxed mode: the
  * caller's allocator may still allocate); abort drops a capture that failed part-way */
 int nqk_graph_begin(void);
@@ -122,6 +134,18 @@ int nqk_relu_q(const void* q, int q_dtype, void* out, int out_dtype, int64_t n, 
  * lda), col[b][n] = sum_k B[b][k][n] (B given TRANSPOSED as Bt[b][n][k], ldb). */
 int nqk_rowsum(const void* a, int dtype, int64_t* out, int64_t batch, int64_t rows, int64_t k,
                int64_t ld, int64_t batch_stride);
+
+/* uint8 images -> the model's input tensor by per-channel table lookup (numpy_quant/images.py:
+ * normalize, layout change and quantize are elementwise per channel, so a uint8 pixel of
+ * channel ci maps to one of 256 values):
+ *   out[ni][ci][y][x] = lut[ci][img[ni][y][x][ci]]   (NQK_IMG_NHWC)
+ *   out[ni][ci][y][x] = lut[ci][img[ni][ci][y][x]]   (NQK_IMG_NCHW)
+ * lut [c][256] and out [n][c][h][w] both of lut_dtype (NQK_I8 .. NQK_I64, NQK_F32); c in 1..4.
+ * With lut = nqk_quantize of the normalized values 0..255 the output is bit-identical to
+ * quantize(normalize(img)); no floating-point arithmetic happens here. */
+enum nqk_image_layout { NQK_IMG_NHWC = 0, NQK_IMG_NCHW = 1 };
+int nqk_image_lut(const uint8_t* img, const void* lut, int lut_dtype, void* out, int64_t n, int64_t h,
+                  int64_t w, int64_t c, int layout);
 
 /* ------------------------------------------------------ L1: q_matmul GEMMs */
 /* q_matmul's integer product, numpy_quantization.py:47:

@@ -16,6 +16,7 @@ hipStream_t g_side[64][kSide] = {};
 int g_cur = 0;                     // current stream index of the (single) host thread
 hipEvent_t g_fork[64] = {}, g_join[64][kSide] = {};  // per device, with that device's side streams
 hipEvent_t g_t0 = nullptr, g_t1 = nullptr;
+hipStream_t g_copy[64] = {};       // the upload stream (nqk_upload_async), created on first use
 hipGraph_t g_capturing = nullptr;
 std::mutex g_mu;
 }  // namespace
@@ -95,7 +96,37 @@ int nqk_memset(void* ptr, int value, size_t bytes) {
 int nqk_sync(void) {
   for (int i = 0; g_device >= 0 && i < kSide; ++i)
     if (g_side[g_device][i] && check(hipStreamSynchronize(g_side[g_device][i]), "hipStreamSynchronize")) return -1;
+  if (g_device >= 0 && g_copy[g_device] && check(hipStreamSynchronize(g_copy[g_device]), "hipStreamSynchronize"))
+    return -1;
   return check(hipStreamSynchronize(g_device >= 0 ? g_streams[g_device] : stream()), "hipStreamSynchronize");
+}
+
+static int ensure_copy() {
+  if (g_device < 0 && nqk_init(0)) return -1;
+  if (!g_copy[g_device] && check(hipStreamCreateWithFlags(&g_copy[g_device], hipStreamNonBlocking), "hipStreamCreate"))
+    return -1;
+  return 0;
+}
+
+int nqk_host_alloc(void** ptr, size_t bytes) {
+  if (!ptr) return fail("nqk_host_alloc: null pointer");
+  if (g_device < 0 && nqk_init(0)) return -1;
+  return check(hipHostMalloc(ptr, bytes ? bytes : 16, hipHostMallocDefault), "hipHostMalloc");
+}
+int nqk_host_free(void* ptr) { return check(hipHostFree(ptr), "hipHostFree"); }
+
+int nqk_upload_async(void* dst, const void* src_pinned, size_t bytes, void* done_event) {
+  if (bytes && (!dst || !src_pinned)) return fail("nqk_upload_async: null pointer");
+  if (ensure_copy()) return -1;
+  if (bytes && check(hipMemcpyAsync(dst, src_pinned, bytes, hipMemcpyHostToDevice, g_copy[g_device]), "upload"))
+    return -1;
+  if (done_event) return check(hipEventRecord((hipEvent_t)done_event, g_copy[g_device]), "hipEventRecord");
+  return 0;
+}
+int nqk_upload_wait_for(void* event) {
+  if (!event) return fail("nqk_upload_wait_for: null event");
+  if (ensure_copy()) return -1;
+  return check(hipStreamWaitEvent(g_copy[g_device], (hipEvent_t)event, 0), "hipStreamWaitEvent");
 }
 
 static int ensure_side() {

@@ -16,6 +16,7 @@ NQK_I8, NQK_I16, NQK_I32, NQK_I64, NQK_F32 = 1, 2, 3, 4, 5
 ZP_NONE, ZP_SCALAR, ZP_ROW, ZP_COL, ZP_KCONST, ZP_FULL = 0, 1, 2, 4, 8, 16
 ADD, SUB, MUL, DIV = 0, 1, 2, 3
 NEG, EXP, ERF, SQRT, RELU, SIGMOID, RECIP, TANH = range(8)
+IMG_NHWC, IMG_NCHW = 0, 1
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -72,6 +73,10 @@ SIGNATURES = {
     "nqk_event_elapsed": [_p, _p, ctypes.POINTER(_f)],
     "nqk_event_destroy": [_p],
     "nqk_event_wait": [_p],
+    "nqk_host_alloc": [ctypes.POINTER(_p), ctypes.c_size_t],
+    "nqk_host_free": [_p],
+    "nqk_upload_async": [_p, _p, ctypes.c_size_t, _p],
+    "nqk_upload_wait_for": [_p],
     "nqk_graph_begin": [],
     "nqk_graph_end": [ctypes.POINTER(_p)],
     "nqk_graph_abort": [],
@@ -80,6 +85,7 @@ SIGNATURES = {
     "nqk_quantize": [_p, _p, _i, _l, _f, _l, _i, _i, _p, _l],
     "nqk_dequantize": [_p, _i, _p, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp],
     "nqk_requantize": [_p, _i, _p, _i, _p, _i, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp, _f, _l, _i, _i],
+    "nqk_image_lut": [_p, _p, _i, _p, _l, _l, _l, _l, _i],
     "nqk_rowsum": [_p, _i, _p, _l, _l, _l, _l, _l],
     "nqk_relu_q": [_p, _i, _p, _i, _l, _l],
     "nqk_qgemm_i8": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],

@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _lib
 from . import onnx_proto
-from .device import sync
+from .device import DeviceArray, sync
+from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
 from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, quantize_tensor, where)
 from . import kernels as K
@@ -194,6 +195,9 @@ class Model:
         self.values = values
         self.inputs = inputs
         self.outputs = outputs
+        # an images.ImagePreprocess: uint8 image batches are then accepted as inputs
+        # (normalized and moved to NCHW on the device); None: uint8 is refused
+        self.image_preprocess = None
 
     def __repr__(self):
         return f"Model({len(self.nodes)} nodes, {len(self.values)} values, inputs={self.inputs}, outputs={self.outputs})"
@@ -268,6 +272,8 @@ class Model:
                 variable.data = FTensor(np.ascontiguousarray(array))
             elif array.dtype == np.int64:
                 variable.data = ITensor(array.copy())
+            elif array.dtype == np.uint8 and self.image_preprocess is not None:
+                variable.data = self.image_preprocess.to_device(array)
             else:
                 raise ValueError(f"Array dtype {array.dtype} not supported")
 
@@ -415,7 +421,9 @@ class Model:
                 raise ValueError(f"blob constant {name}: bit width {qvalues[name].data.bit_width}, the graph needs {bw}")
         qoutputs = [qvalues[o.name] for o in self.outputs]
         qinputs = [qvalues[i.name] for i in self.inputs]
-        return QModel(list(qnodes.values()), list(qvalues.values()), qinputs, qoutputs, bit_width, qp)
+        qmodel = QModel(list(qnodes.values()), list(qvalues.values()), qinputs, qoutputs, bit_width, qp)
+        qmodel.image_preprocess = self.image_preprocess
+        return qmodel
 
 
 class QModel(Model):
@@ -424,6 +432,7 @@ class QModel(Model):
         self.bit_width = bit_width
         self.quant_params = quant_params
         self._deq_cache: dict[str, FTensor] = {}
+        self._image_luts: dict[str, QuantLut] = {}  # per uint8 input (image_preprocess)
         self._plan = None
         # QModel.__call__ compiles the fused plan on first use (NQK_FUSE=0: never);
         # keep_values = True runs the reference's node loop instead, so every
@@ -459,8 +468,75 @@ class QModel(Model):
                                                 qp.zero_point)
             elif array.dtype == np.int64:
                 variable.data = ITensor(array)
+            elif array.dtype == np.uint8 and self.image_preprocess is not None:
+                self.image_preprocess.check(array)
+                self._set_images(variable, DeviceArray.from_host(array), array.shape)
             else:
                 raise ValueError(f"Array dtype {array.dtype} not supported")
+
+    def _set_images(self, variable, images_dev, shape):
+        """The input QTensor of a uint8 batch on the device: one table lookup writes what
+        quantize_tensor(FTensor(image_preprocess.reference(images))) would."""
+        pre = self.image_preprocess
+        qp = self.quant_params[variable.name]
+        lut = self._image_luts.setdefault(variable.name, QuantLut()).get(pre, self.bit_width, qp.scale, qp.zero_point)
+        variable.data = QTensor(pre.lookup(images_dev, shape, lut), self.bit_width, scale=qp.scale,
+                                zero_point=qp.zero_point)
+
+    def classify_stream(self, batches):
+        """Iterator of the model's first output for an iterable of uint8 image batches, in
+        order, equal to `qmodel([batch])[0]` of each.  Batch k + 1 is copied into one of two
+        pinned host buffers and uploaded on the library's copy stream while batch k computes;
+        the lookup kernel waits for its batch's copy, and a copy into a staging buffer waits
+        for the kernel that last read it.  A batch the model refuses raises what
+        `qmodel([batch])` raises, after the results of the batches before it were handed
+        out; the library is back on stream 0 then."""
+        pre = self.image_preprocess
+        if pre is None:
+            raise ValueError("classify_stream: set qmodel.image_preprocess first")
+        if len(self.inputs) != 1:
+            raise ValueError("classify_stream: a model with one (image) input")
+        if not self.keep_values and self._plan is None and self.fuse:
+            self.compile()
+        variable = self.inputs[0]
+        slots = [UploadSlot(), UploadSlot()]
+
+        def stage(k, batch):
+            pre.check(batch)
+            slots[k % 2].upload(batch)
+
+        try:
+            it = iter(batches)
+            k = 0
+            try:
+                stage(0, next(it))
+            except StopIteration:
+                return
+            while True:
+                slot = slots[k % 2]
+                self._set_images(variable, slot.images(), slot.shape)
+                slot.consumed()
+                self.run(eager=self.keep_values)
+                # batch k is issued: stage batch k + 1 beside it; an error of that batch is
+                # raised after batch k's result went out
+                more, failure = True, None
+                try:
+                    stage(k + 1, next(it))
+                except StopIteration:
+                    more = False
+                except Exception as e:  # noqa: BLE001
+                    failure = e
+                yield self.outputs_device()[0].data
+                if failure is not None:
+                    raise failure
+                if not more:
+                    return
+                k += 1
+        finally:
+            _lib.call("nqk_set_stream", 0)
+            sync()  # no upload in flight when the pinned buffers go
+            for slot in slots:
+                slot.close()
 
     def compile(self):
         """Build the fused device plan (plan.py): matched transformer layers run as
