@@ -146,6 +146,33 @@ int nqk_rowsum(const void* a, int dtype, int64_t* out, int64_t batch, int64_t ro
 enum nqk_image_layout { NQK_IMG_NHWC = 0, NQK_IMG_NCHW = 1 };
 int nqk_image_lut(const uint8_t* img, const void* lut, int lut_dtype, void* out, int64_t n, int64_t h,
                   int64_t w, int64_t c, int layout);
+/* Ragged uint8 HWC images -> resize -> center crop -> the same table lookup, in one kernel
+ * (numpy_quant/images.py ResizeCrop).  The resize is Pillow's 8-bit Image.resize(BILINEAR): a
+ * horizontal and then a vertical pass, each acc = 1 << 21; acc += pixel * weight (int32, weights in
+ * 22-bit fixed point, computed by the caller); clip(acc >> 22, 0, 255).  With u8 the result of both
+ * passes,   out[ni][ci][y][x] = lut[ci][u8[ni][y][x][ci]],   out [n][c][oh][ow] of lut_dtype.
+ * pixels: the images back to back, HWC, no alignment assumed, pixel_bytes in all.
+ * meta (meta_bytes, 8-byte aligned): n descriptors nqk_resize_image, then an int32 tap blob.  xtab
+ * and ytab are the word index in that blob of the image's horizontal / vertical tap table:
+ *   ksize, count, bounds[count][2] = (first input index, taps n), weights[count][ksize]
+ * with count = ow (oh): the table holds the crop window's coordinates only, so images of one size
+ * share tables.  meta_dev is what the kernel reads; meta_host is a host-readable copy of the same
+ * bytes (the pinned staging buffer of nqk_upload_async), from which everything that could become an
+ * out-of-range read is checked before the launch: image extents within pixel_bytes, table indices
+ * and extents within the blob, first >= 0, first + n <= w (h), n <= ksize <= NQK_RESIZE_MAX_TAPS,
+ * 255 * sum|weights| + 2^21 < 2^31 per coordinate, 1 <= c <= 4.  A workgroup resizes a tile of at
+ * most 16 output rows through LDS; the rows one output row needs, n * round_up(ow, 16) * c bytes,
+ * must fit NQK_RESIZE_LDS_BYTES. */
+#define NQK_RESIZE_MAX_TAPS 65
+#define NQK_RESIZE_LDS_BYTES (56 << 10)
+typedef struct nqk_resize_image {
+  int64_t offset;      /* of the image's first byte in pixels */
+  int32_t h, w;        /* source size */
+  int32_t xtab, ytab;  /* tap tables (word index in the blob) */
+} nqk_resize_image;
+int nqk_image_resize_lut(const uint8_t* pixels, int64_t pixel_bytes, const void* meta_dev, const void* meta_host,
+                         int64_t meta_bytes, const void* lut, int lut_dtype, void* out, int64_t n, int64_t c,
+                         int64_t oh, int64_t ow);
 
 /* ------------------------------------------------------ L1: q_matmul GEMMs */
 /* q_matmul's integer product, numpy_quantization.py:47:

@@ -86,6 +86,7 @@ SIGNATURES = {
     "nqk_dequantize": [_p, _i, _p, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp],
     "nqk_requantize": [_p, _i, _p, _i, _p, _i, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp, _f, _l, _i, _i],
     "nqk_image_lut": [_p, _p, _i, _p, _l, _l, _l, _l, _i],
+    "nqk_image_resize_lut": [_p, _l, _p, _p, _l, _p, _i, _p, _l, _l, _l, _l],
     "nqk_rowsum": [_p, _i, _p, _l, _l, _l, _l, _l],
     "nqk_relu_q": [_p, _i, _p, _i, _l, _l],
     "nqk_qgemm_i8": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],

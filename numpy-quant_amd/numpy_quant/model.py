@@ -74,6 +74,17 @@ class QuantizationParams:
         return f"QuantizationParams(scale={self.scale}, zero_point={self.zero_point})"
 
 
+def _is_image_list(array, pre) -> bool:
+    """Whether an input goes through `pre.resize` (images.ResizeCrop): a list or tuple of
+    images (ValueError when no resize is configured) or a uint8 array when one is."""
+    resize = getattr(pre, "resize", None)
+    if isinstance(array, (list, tuple)):
+        if resize is None:
+            raise ValueError("A list of images is not supported without image_preprocess.resize (images.ResizeCrop)")
+        return True
+    return resize is not None and isinstance(array, np.ndarray) and array.dtype == np.uint8
+
+
 def _listing(kind: str, fields) -> str:
     """Readable multi-line dump of an IR object: one line per element of each list or
     dict field (the reference prints its models this way, model.py:223-234, 464-484)."""
@@ -268,7 +279,9 @@ class Model:
 
     def _set_inputs(self, inputs):
         for array, variable in zip(inputs, self.inputs):
-            if array.dtype == np.float32:
+            if _is_image_list(array, self.image_preprocess):
+                variable.data = self.image_preprocess.to_device(array)
+            elif array.dtype == np.float32:
                 variable.data = FTensor(np.ascontiguousarray(array))
             elif array.dtype == np.int64:
                 variable.data = ITensor(array.copy())
@@ -461,7 +474,11 @@ class QModel(Model):
     def set_inputs(self, inputs: List[np.ndarray]):
         for array, variable in zip(inputs, self.inputs):
             qp = self.quant_params[variable.name]
-            if isinstance(array, FTensor):
+            if _is_image_list(array, self.image_preprocess):
+                pre = self.image_preprocess
+                variable.data = QTensor(pre.resize_lookup_host(array, self._image_lut(variable)), self.bit_width,
+                                        scale=qp.scale, zero_point=qp.zero_point)
+            elif isinstance(array, FTensor):
                 variable.data = quantize_tensor(array, self.bit_width, qp.scale, qp.zero_point)
             elif array.dtype == np.float32:
                 variable.data = quantize_tensor(FTensor(np.ascontiguousarray(array)), self.bit_width, qp.scale,
@@ -474,19 +491,35 @@ class QModel(Model):
             else:
                 raise ValueError(f"Array dtype {array.dtype} not supported")
 
+    def _image_lut(self, variable) -> DeviceArray:
+        """The quantized table of this input (images.QuantLut)"""
+        qp = self.quant_params[variable.name]
+        return self._image_luts.setdefault(variable.name, QuantLut()).get(self.image_preprocess, self.bit_width,
+                                                                          qp.scale, qp.zero_point)
+
     def _set_images(self, variable, images_dev, shape):
         """The input QTensor of a uint8 batch on the device: one table lookup writes what
         quantize_tensor(FTensor(image_preprocess.reference(images))) would."""
         pre = self.image_preprocess
         qp = self.quant_params[variable.name]
-        lut = self._image_luts.setdefault(variable.name, QuantLut()).get(pre, self.bit_width, qp.scale, qp.zero_point)
-        variable.data = QTensor(pre.lookup(images_dev, shape, lut), self.bit_width, scale=qp.scale,
-                                zero_point=qp.zero_point)
+        variable.data = QTensor(pre.lookup(images_dev, shape, self._image_lut(variable)), self.bit_width,
+                                scale=qp.scale, zero_point=qp.zero_point)
+
+    def _set_slot(self, variable, slot):
+        """_set_images of classify_stream's staged batch (a RaggedBatch goes through the resize
+        kernel, which checks its descriptors in the slot's pinned copy)."""
+        if slot.batch is None:
+            return self._set_images(variable, slot.images(), slot.shape)
+        pre = self.image_preprocess
+        qp = self.quant_params[variable.name]
+        out = pre.lookup_resized(slot.images(), slot.batch, slot.host.ptr, self._image_lut(variable))
+        variable.data = QTensor(out, self.bit_width, scale=qp.scale, zero_point=qp.zero_point)
 
     def classify_stream(self, batches):
-        """Iterator of the model's first output for an iterable of uint8 image batches, in
-        order, equal to `qmodel([batch])[0]` of each.  Batch k + 1 is copied into one of two
-        pinned host buffers and uploaded on the library's copy stream while batch k computes;
+        """Iterator of the model's first output for an iterable of uint8 image batches (with
+        `image_preprocess.resize`: of lists of HWC images, packed with their descriptors and
+        taps into the one pinned buffer), in order, equal to `qmodel([batch])[0]` of each.
+        Batch k + 1 is copied into one of two pinned host buffers and uploaded on the library's copy stream while batch k computes;
         the lookup kernel waits for its batch's copy, and a copy into a staging buffer waits
         for the kernel that last read it.  A batch the model refuses raises what
         `qmodel([batch])` raises, after the results of the batches before it were handed
@@ -502,7 +535,10 @@ class QModel(Model):
         slots = [UploadSlot(), UploadSlot()]
 
         def stage(k, batch):
-            pre.check(batch)
+            if pre.resize is not None:
+                batch = pre.pack(batch)  # checks it
+            else:
+                pre.check(batch)
             slots[k % 2].upload(batch)
 
         try:
@@ -514,7 +550,7 @@ class QModel(Model):
                 return
             while True:
                 slot = slots[k % 2]
-                self._set_images(variable, slot.images(), slot.shape)
+                self._set_slot(variable, slot)
                 slot.consumed()
                 self.run(eager=self.keep_values)
                 # batch k is issued: stage batch k + 1 beside it; an error of that batch is
