@@ -265,7 +265,10 @@ int nqk_binary_f32(int op, const float* a, const float* b, float* out, int ndim,
 enum nqk_unop { NQK_NEG = 0, NQK_EXP = 1, NQK_ERF = 2, NQK_SQRT = 3, NQK_RELU = 4,
                 NQK_SIGMOID = 5, NQK_RECIP = 6, NQK_TANH = 7 };
 /* NumPy-exact where it matters: EXP is numpy's AVX512F float32 exp algorithm
- * (bit-identical to np.exp on all 2^32 inputs), ERF is numpy_helper.py:95-112. */
+ * (bit-identical to np.exp on all 2^32 inputs), ERF is numpy_helper.py:95-112.
+ * TANH is the one float op that is not bit-pinned: it is the device library's tanhf, NumPy's
+ * is another implementation; both are held to the same ulp bound against a float64 tanh
+ * (parity) and agree exactly at +-0, +-inf, NaN and in saturation. */
 int nqk_unary_f32(int op, const float* x, float* out, int64_t n);
 /* x + scalar (FTensor.__add__ with a Python float, tensor.py:158-164) */
 int nqk_add_scalar_f32(const float* x, float s, float* out, int64_t n);
@@ -276,6 +279,14 @@ int nqk_layernorm_lastdim(const float* x, const float* gamma, const float* beta,
                           int64_t rows, int64_t cols, float eps);
 /* mean over the last axis with NumPy's pairwise summation (np.mean f32) */
 int nqk_mean_lastdim(const float* x, float* out, int64_t rows, int64_t cols);
+/* The same three reductions over the middle axis of a contiguous [outer, n, inner] array with
+ * inner > 1.  NumPy adds such an axis one term at a time in index order, starting from +0
+ * (pairwise summation is for an innermost axis only), and so do these; n has no upper limit.
+ * nqk_normalize_axis writes (x - mean) * (1 / sqrt(var + eps)); LayerNormalization's scale and
+ * bias follow as a broadcast nqk_binary_f32 multiply and add (model.py:141-150). */
+int nqk_mean_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner);
+int nqk_softmax_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner);
+int nqk_normalize_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner, float eps);
 /* global min and max (calibration, model.py:333-336) -> out[0]=min, out[1]=max */
 int nqk_minmax_f32(const float* x, int64_t n, float* out2, float* scratch, int64_t scratch_len);
 /* N-d strided copy for Transpose / Concat / Slice / Expand / Gather / padding

@@ -8,7 +8,10 @@
 //     (checked exhaustively on the host, tests/test_numerics.py on the GPU);
 //   * sums / means over the last axis follow NumPy's pairwise summation
 //     (blocks of <= 128 with 8 interleaved accumulators, recursive halving at
-//     multiples of 8), so LayerNormalization and Softmax match bit for bit.
+//     multiples of 8), so LayerNormalization and Softmax match bit for bit;
+//   * sums / means over an axis with elements after it are added one term at a time
+//     in index order from +0, as NumPy adds them (the k_*_axis kernels);
+//   * tanh is the device library's tanhf: the one op here that is not bit-pinned.
 #include "nqk_common.h"
 #include "nqk_numerics.h"
 
@@ -154,7 +157,7 @@ k_layernorm(const float* __restrict__ x, const float* __restrict__ g, const floa
     const float* xr = x + r * cols;
     for (int64_t i = lane; i < cols; i += 64) v[i] = xr[i];
     __syncthreads();
-    const float mean = row_pairwise_sum(v, p, part, leafv) / fcols;
+    const float mean = (0.0f + row_pairwise_sum(v, p, part, leafv)) / fcols;  // NumPy's reduce starts at +0
     const float nmean = -mean;
     for (int64_t i = lane; i < cols; i += 64) {
       float d = v[i] + nmean;
@@ -182,9 +185,72 @@ k_mean_rows(const float* __restrict__ x, float* __restrict__ out, int64_t rows, 
   for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
     for (int64_t i = lane; i < cols; i += 64) v[i] = x[r * cols + i];
     __syncthreads();
-    float s = row_pairwise_sum(v, p, part, leafv);
+    float s = 0.0f + row_pairwise_sum(v, p, part, leafv);  // NumPy's reduce starts at +0: a sum of -0 is +0
     if (lane == 0) out[r] = s / (float)cols;
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------ reductions over an inner axis
+// x is contiguous [outer, n, inner] with inner > 1 and the middle axis is reduced.  NumPy runs
+// such a reduction as n elementwise adds into an output that starts at +0, so every output is
+// (((+0 + x[0]) + x[1]) + ...) in index order — not the pairwise order of the row kernels.
+// One thread per (outer, inner) output; neighbouring threads read neighbouring addresses.
+__device__ __forceinline__ float axis_sum(const float* __restrict__ p, int64_t n, int64_t inner) {
+  float s = 0.0f;
+  for (int64_t k = 0; k < n; ++k) s = s + p[k * inner];
+  return s;
+}
+
+__global__ void k_mean_axis(const float* __restrict__ x, float* __restrict__ out, int64_t outer, int64_t n,
+                            int64_t inner) {
+  const int64_t total = outer * inner, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t o = t / inner, i = t - o * inner;
+    out[t] = axis_sum(x + o * n * inner + i, n, inner) / (float)n;
+  }
+}
+
+__global__ void k_softmax_axis(const float* __restrict__ x, float* __restrict__ out, int64_t outer, int64_t n,
+                               int64_t inner) {
+  const int64_t total = outer * inner, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t o = t / inner, i = t - o * inner;
+    const float* xp = x + o * n * inner + i;
+    float* op = out + o * n * inner + i;
+    float mx = -__builtin_inff();
+    for (int64_t k = 0; k < n; ++k) {
+      const float v = xp[k * inner];
+      mx = v > mx ? v : mx;
+    }
+    const float nm = -mx;
+    float s = 0.0f;
+    for (int64_t k = 0; k < n; ++k) {
+      const float e = np_expf(xp[k * inner] + nm);
+      op[k * inner] = e;
+      s = s + e;
+    }
+    for (int64_t k = 0; k < n; ++k) op[k * inner] = op[k * inner] / s;
+  }
+}
+
+// out = (x - mean) * (1 / sqrt(var + eps)): stage 1 of LayerNormalization (model.py:141-147);
+// scale and bias are applied by the caller's broadcast multiply and add
+__global__ void k_normalize_axis(const float* __restrict__ x, float* __restrict__ out, int64_t outer, int64_t n,
+                                 int64_t inner, float eps) {
+  const int64_t total = outer * inner, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t o = t / inner, i = t - o * inner;
+    const float* xp = x + o * n * inner + i;
+    float* op = out + o * n * inner + i;
+    const float nmean = -(axis_sum(xp, n, inner) / (float)n);
+    float s = 0.0f;
+    for (int64_t k = 0; k < n; ++k) {
+      const float d = xp[k * inner] + nmean;
+      s = s + d * d;
+    }
+    const float inv = 1.0f / __builtin_sqrtf(s / (float)n + eps);
+    for (int64_t k = 0; k < n; ++k) op[k * inner] = (xp[k * inner] + nmean) * inv;
   }
 }
 
@@ -425,6 +491,29 @@ extern "C" int nqk_mean_lastdim(const float* x, float* out, int64_t rows, int64_
   if (row_plan(cols, p)) return -1;
   hipLaunchKernelGGL(k_mean_rows, dim3(row_grid(rows)), dim3(64), row_smem(cols), stream(), x, out, rows, cols, p);
   return launch_status("nqk_mean_lastdim");
+}
+
+extern "C" int nqk_mean_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner) {
+  if (outer < 0 || n <= 0 || inner <= 0) return fail("nqk_mean_axis: bad extents");
+  if (outer * inner == 0) return 0;
+  hipLaunchKernelGGL(k_mean_axis, dim3(grid_for(outer * inner)), dim3(kThreads), 0, stream(), x, out, outer, n, inner);
+  return launch_status("nqk_mean_axis");
+}
+
+extern "C" int nqk_softmax_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner) {
+  if (outer < 0 || n <= 0 || inner <= 0) return fail("nqk_softmax_axis: bad extents");
+  if (outer * inner == 0) return 0;
+  hipLaunchKernelGGL(k_softmax_axis, dim3(grid_for(outer * inner)), dim3(kThreads), 0, stream(), x, out, outer, n,
+                     inner);
+  return launch_status("nqk_softmax_axis");
+}
+
+extern "C" int nqk_normalize_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner, float eps) {
+  if (outer < 0 || n <= 0 || inner <= 0) return fail("nqk_normalize_axis: bad extents");
+  if (outer * inner == 0) return 0;
+  hipLaunchKernelGGL(k_normalize_axis, dim3(grid_for(outer * inner)), dim3(kThreads), 0, stream(), x, out, outer, n,
+                     inner, eps);
+  return launch_status("nqk_normalize_axis");
 }
 
 extern "C" int nqk_minmax_f32(const float* x, int64_t n, float* out2, float* scratch, int64_t scratch_len) {

@@ -102,6 +102,9 @@ SIGNATURES = {
     "nqk_softmax_lastdim": [_p, _p, _l, _l],
     "nqk_layernorm_lastdim": [_p, _p, _p, _p, _l, _l, _f],
     "nqk_mean_lastdim": [_p, _p, _l, _l],
+    "nqk_mean_axis": [_p, _p, _l, _l, _l],
+    "nqk_softmax_axis": [_p, _p, _l, _l, _l],
+    "nqk_normalize_axis": [_p, _p, _l, _l, _l, _f],
     "nqk_minmax_f32": [_p, _l, _p, _p, _l],
     "nqk_copy_strided": [_p, _p, _i, _i, _lp, _lp, _lp],
     "nqk_where_f32": [_p, _p, _p, _p, _i, _lp, _lp, _lp, _lp],

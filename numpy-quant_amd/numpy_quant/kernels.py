@@ -455,50 +455,84 @@ def add_scalar(x: DeviceArray, s: float) -> DeviceArray:
     return out
 
 
-def _move_last(x: DeviceArray, axis: int):
+def _axis_split(x: DeviceArray, axis: int):
+    """(outer, n, inner) of a contiguous array around `axis`.  NumPy sums an axis that still
+    has elements after it (inner > 1) one term at a time in index order; only an effectively
+    innermost axis (inner == 1: trailing extents of 1 dropped) gets pairwise summation."""
+    if not -x.ndim <= axis < x.ndim:
+        raise ValueError(f"axis {axis} is out of bounds for array of dimension {x.ndim}")
     axis %= x.ndim
-    if axis == x.ndim - 1:
-        return x, None
-    perm = [k for k in range(x.ndim) if k != axis] + [axis]
-    from .device import permute
-    return permute(x, perm), perm
+    return int(math.prod(x.shape[:axis])), x.shape[axis], int(math.prod(x.shape[axis + 1:]))
 
 
-def _move_back(y: DeviceArray, perm):
-    if perm is None:
-        return y
-    inv = [0] * len(perm)
-    for i, p in enumerate(perm):
-        inv[p] = i
-    from .device import permute
-    return permute(y, inv)
+# longest innermost axis of the pairwise row kernels (nqk_numerics.h: 64 leaves of 128)
+MAX_ROW = 8192
+
+
+def _check_row(cols: int) -> None:
+    if cols > MAX_ROW:
+        raise ValueError(f"reduction over an innermost axis of {cols} elements: the pairwise-sum plan "
+                         f"covers at most {MAX_ROW}")
 
 
 def softmax(x: DeviceArray, axis: int) -> DeviceArray:
-    xt, perm = _move_last(x, axis)
-    cols = xt.shape[-1]
-    out = DeviceArray(xt.shape, np.float32)
-    _lib.call("nqk_softmax_lastdim", xt.vp, out.vp, xt.size // max(cols, 1), cols)
-    return _move_back(out, perm)
+    outer, n, inner = _axis_split(x, axis)
+    out = DeviceArray(x.shape, np.float32)
+    if x.size == 0:
+        return out
+    if inner == 1:
+        _check_row(n)
+        _lib.call("nqk_softmax_lastdim", x.vp, out.vp, outer, n)
+    else:
+        _lib.call("nqk_softmax_axis", x.vp, out.vp, outer, n, inner)
+    return out
 
 
 def layernorm(x: DeviceArray, g: DeviceArray, b: DeviceArray, axis: int, eps: float) -> DeviceArray:
-    xt, perm = _move_last(x, axis)
-    cols = xt.shape[-1]
-    if g.size != cols or b.size != cols:
-        g = materialize_broadcast(g, (cols,)) if g.size == 1 else g
-        b = materialize_broadcast(b, (cols,)) if b.size == 1 else b
-    if g.size != cols or b.size != cols:
-        raise ValueError("LayerNormalization scale/bias must cover the normalised axis")
-    out = DeviceArray(xt.shape, np.float32)
-    _lib.call("nqk_layernorm_lastdim", xt.vp, g.vp, b.vp, out.vp, xt.size // cols, cols, float(np.float32(eps)))
-    return _move_back(out, perm)
+    """model.py:134-152.  Scale and bias broadcast against x as NumPy broadcasts them."""
+    outer, n, inner = _axis_split(x, axis)
+    axis %= x.ndim
+    eps = float(np.float32(eps))
+    out_shape = tuple(np.broadcast_shapes(x.shape, g.shape, b.shape))
+    if x.size == 0:
+        return DeviceArray(out_shape, np.float32)
+    if inner > 1:
+        norm = DeviceArray(x.shape, np.float32)
+        _lib.call("nqk_normalize_axis", x.vp, norm.vp, outer, n, inner, eps)
+        return binary(_lib.ADD, binary(_lib.MUL, norm, g), b)
+    # innermost axis: the row kernel applies a scale and bias that vary along that axis alone
+    _check_row(n)
+    along = (1,) * axis + (n,) + (1,) * (x.ndim - 1 - axis)
+    for t in (g, b):
+        if t.size != 1 and (t.ndim > x.ndim or (1,) * (x.ndim - t.ndim) + t.shape != along):
+            raise ValueError("LayerNormalization scale/bias must cover the normalised axis "
+                             f"({t.shape} against {x.shape}, axis {axis})")
+    if out_shape != x.shape:
+        raise ValueError(f"LayerNormalization scale/bias of more dimensions than the input {x.shape}")
+    if g.size != n:
+        g = materialize_broadcast(g.reshape(()), (n,))
+    if b.size != n:
+        b = materialize_broadcast(b.reshape(()), (n,))
+    out = DeviceArray(x.shape, np.float32)
+    _lib.call("nqk_layernorm_lastdim", x.vp, g.vp, b.vp, out.vp, outer, n, eps)
+    return out
 
 
-def mean_lastdim(x: DeviceArray) -> DeviceArray:
-    cols = x.shape[-1]
-    out = DeviceArray(x.shape[:-1] + (1,), np.float32)
-    _lib.call("nqk_mean_lastdim", x.vp, out.vp, x.size // cols, cols)
+def mean_axis(x: DeviceArray, axis: int, keepdims: bool) -> DeviceArray:
+    """np.mean(x, axis, keepdims=keepdims) for float32 (tensor.py:127-128)."""
+    outer, n, inner = _axis_split(x, axis)
+    axis %= x.ndim
+    shape = x.shape[:axis] + ((1,) if keepdims else ()) + x.shape[axis + 1:]
+    if n == 0:
+        raise ValueError("mean of an empty axis")
+    out = DeviceArray(shape, np.float32)
+    if out.size == 0:
+        return out
+    if inner == 1:
+        _check_row(n)
+        _lib.call("nqk_mean_lastdim", x.vp, out.vp, outer, n)
+    else:
+        _lib.call("nqk_mean_axis", x.vp, out.vp, outer, n, inner)
     return out
 
 
@@ -516,6 +550,8 @@ def where(cond: np.ndarray, a: DeviceArray, b: DeviceArray) -> DeviceArray:
     out = DeviceArray(out_shape, np.float32)
     sc, sa, sb = (broadcast_strides(t.shape, out_shape) for t in (c, a, b))
     shp, (sc, sa, sb) = collapse(out_shape, sc, sa, sb)
+    if len(shp) > 6:
+        raise ValueError("elementwise op over more than 6 non-mergeable dimensions")
     _lib.call("nqk_where_f32", c.vp, a.vp, b.vp, out.vp, len(shp), _lib.i64arr(shp), _lib.i64arr(sc),
               _lib.i64arr(sa), _lib.i64arr(sb))
     return out

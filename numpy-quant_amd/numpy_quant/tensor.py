@@ -162,17 +162,7 @@ class FTensor:
         return FTensor(K.unary(_lib.RECIP, self.dev))
 
     def mean(self, axis: int, keepdims: bool):
-        axis = axis % self.dev.ndim
-        x = self.dev
-        if axis != x.ndim - 1:
-            perm = [k for k in range(x.ndim) if k != axis] + [axis]
-            x = permute(x, perm)
-        m = K.mean_lastdim(x)
-        shape = list(self.dev.shape)
-        shape[axis] = 1
-        if not keepdims:
-            shape.pop(axis)
-        return FTensor(m.reshape(shape))
+        return FTensor(K.mean_axis(self.dev, axis, bool(keepdims)))
 
     def relu(self):
         return FTensor(K.unary(_lib.RELU, self.dev))
