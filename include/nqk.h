@@ -274,6 +274,21 @@ int nqk_unary_f32(int op, const float* x, float* out, int64_t n);
 int nqk_add_scalar_f32(const float* x, float s, float* out, int64_t n);
 /* Softmax over the last axis (tensor.py:211-218): e = exp(x - max); e / pairwise_sum(e) */
 int nqk_softmax_lastdim(const float* x, float* out, int64_t rows, int64_t cols);
+/* Top-k of every row with the Softmax probabilities of the selected elements, in one kernel
+ * (QModel.classify; the reference leaves this step to its callers).  x [rows][ldx], cols <= ldx
+ * used, of x_dtype NQK_F32 or NQK_I8 .. NQK_I64.  An integer row is first dequantized as
+ * nqk_dequantize does with a scalar (has_zp) or no zero point, y = f32(f64(q - zp) * f64(scale));
+ * for f32, y = x and scale / zp are ignored.  Per row:
+ *   idx[r][:]   = np.argsort(-y, kind="stable")[:k]: larger first, equal values (-0 == +0) by
+ *                 increasing column, NaNs after every number by increasing column;
+ *   value[r][j] = y[idx[r][j]];
+ *   prob[r][j]  = the bits nqk_softmax_lastdim writes at [r][idx[r][j]] (same row max, exp,
+ *                 pairwise sum and divide).
+ * idx [rows][k] int64; prob and value [rows][k] f32, each may be NULL (prob = NULL skips the exp
+ * and the sum).  Nothing else is written.  1 <= k <= min(cols, 64), cols <= 8192 (the pairwise
+ * plan), ldx >= cols, rows >= 0 (0: nothing to do); anything else fails before a launch. */
+int nqk_topk_softmax(const void* x, int x_dtype, float scale, int64_t zp, int has_zp, int64_t rows,
+                     int64_t cols, int64_t ldx, int k, int64_t* idx, float* prob, float* value);
 /* LayerNormalization over the last axis (model.py:134-152), NumPy pairwise means */
 int nqk_layernorm_lastdim(const float* x, const float* gamma, const float* beta, float* out,
                           int64_t rows, int64_t cols, float eps);

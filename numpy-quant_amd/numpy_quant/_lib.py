@@ -100,6 +100,7 @@ SIGNATURES = {
     "nqk_unary_f32": [_i, _p, _p, _l],
     "nqk_add_scalar_f32": [_p, _f, _p, _l],
     "nqk_softmax_lastdim": [_p, _p, _l, _l],
+    "nqk_topk_softmax": [_p, _i, _f, _l, _i, _l, _l, _l, _i, _p, _p, _p],
     "nqk_layernorm_lastdim": [_p, _p, _p, _p, _l, _l, _f],
     "nqk_mean_lastdim": [_p, _p, _l, _l],
     "nqk_mean_axis": [_p, _p, _l, _l, _l],

@@ -36,14 +36,18 @@ from .tensor import FTensor
 
 class DeviceGraph:
     """`DeviceGraph(qmodel, example_inputs)`; then `g(inputs)` (host arrays out, as
-    `QModel.__call__`) or `g.run_device(inputs)` (the captured output tensors)."""
+    `QModel.__call__`) or `g.run_device(inputs)` (the captured output tensors).
+    With `topk=k` the top-k kernel of `QModel.classify` is captured behind the forward, and
+    both return `[indices, probabilities]` of the first output ([B, k] each) in place of the
+    logits."""
 
-    def __init__(self, qmodel, example_inputs: Sequence[Union[np.ndarray, FTensor]]):
+    def __init__(self, qmodel, example_inputs: Sequence[Union[np.ndarray, FTensor]], topk=None):
         _lib.ensure_init()
         from . import kernels as KM
         if KM.TIMER is not None:
             raise RuntimeError("DeviceGraph: kernels.TIMER is active; its events would be frozen into the graph")
         self.q = qmodel
+        self.topk = topk
         self.staging: List[FTensor] = []
         for a in example_inputs:
             if isinstance(a, FTensor):
@@ -57,7 +61,7 @@ class DeviceGraph:
             from .plan import compile_plan
             self.plan = compile_plan(qmodel)
         self.exec = ctypes.c_void_p()
-        self.outs: List[FTensor] = []
+        self.outs: list = []  # FTensors; with topk [DeviceITensor, FTensor]
         self.blocks = []
         saved = qmodel._plan
         qmodel._plan = self.plan
@@ -79,9 +83,12 @@ class DeviceGraph:
                 self.blocks, POOL.capture = POOL.capture, None
             qmodel._plan = saved
 
-    def _forward(self) -> List[FTensor]:
+    def _forward(self) -> list:
         self.q.set_inputs(self.staging)
         self.q.run(eager=self.plan is None)
+        if self.topk is not None:
+            from .model import _topk_output
+            return list(_topk_output(self.q.outputs[0].data, self.topk))
         return self.q.outputs_device()
 
     def _load(self, inputs) -> None:
@@ -97,7 +104,7 @@ class DeviceGraph:
                 a = np.ascontiguousarray(a, dtype=np.float32)
                 _lib.call("nqk_memcpy_h2d", s.dev.vp, a.ctypes.data_as(ctypes.c_void_p), s.dev.nbytes)
 
-    def run_device(self, inputs) -> List[FTensor]:
+    def run_device(self, inputs) -> list:
         """Replay on device-resident (or host) inputs; returns the captured outputs."""
         if not self.exec:
             raise RuntimeError("DeviceGraph: destroyed")

@@ -488,6 +488,53 @@ def softmax(x: DeviceArray, axis: int) -> DeviceArray:
     return out
 
 
+TOPK_MAX_K = 64       # one winner per lane of the row's wave (nqk_topk.hip)
+TOPK_MAX_COLS = 8192  # the pairwise-sum plan's limit, as for the other row kernels
+
+
+def topk_softmax(x: DeviceArray, k: int, scale=None, zp=None, prob: bool = True, value: bool = False):
+    """Top-k of the last axis with the Softmax probabilities of the selected elements
+    (nqk_topk_softmax): `(indices int64, probabilities | None, values | None)`, each a
+    DeviceArray of shape x.shape[:-1] + (k,).
+
+    x is float32 (scale and zp stay None) or the integer storage of a QTensor with its
+    `scale` and scalar (or no) zero point; the integer form equals the float form on
+    `dequantize(x, scale, zp)` without materialising it.  Per row,
+    indices = np.argsort(-y, kind="stable")[:k] and probabilities are the bits `softmax(y, -1)`
+    holds at those indices.  Every argument is checked here, before the library is touched."""
+    if isinstance(zp, ZpTerm):
+        raise ValueError("topk_softmax: a q_matmul zero-point term (ZpTerm) is not supported; requantize first")
+    if zp is not None and np.ndim(zp):
+        raise ValueError("topk_softmax: the zero point must be a scalar or None")
+    if x.ndim < 1:
+        raise ValueError("topk_softmax: the input needs at least one axis")
+    if x.dtype == np.float32:
+        if scale is not None or zp is not None:
+            raise ValueError("topk_softmax: scale and zero point belong to integer input only")
+    elif x.dtype.kind == "i" and x.dtype in (np.int8, np.int16, np.int32, np.int64):
+        if scale is None:
+            raise ValueError("topk_softmax: integer input needs its scale")
+    else:
+        raise ValueError(f"topk_softmax: dtype {x.dtype} not supported (float32 or int8 / int16 / int32 / int64)")
+    cols = x.shape[-1]
+    rows = int(math.prod(x.shape[:-1]))
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"topk_softmax: k must be an integer, not {type(k).__name__}")
+    k = int(k)
+    if cols > TOPK_MAX_COLS:
+        raise ValueError(f"topk_softmax: rows of {cols} elements (at most {TOPK_MAX_COLS})")
+    if not 1 <= k <= min(cols, TOPK_MAX_K):
+        raise ValueError(f"topk_softmax: k = {k} outside 1..min(cols = {cols}, {TOPK_MAX_K})")
+    shape = x.shape[:-1] + (k,)
+    idx = DeviceArray(shape, np.int64)
+    p = DeviceArray(shape, np.float32) if prob else None
+    v = DeviceArray(shape, np.float32) if value else None
+    _lib.call("nqk_topk_softmax", x.vp, x.code, float(np.float32(1.0 if scale is None else scale)),
+              0 if zp is None else int(zp), 0 if zp is None else 1, rows, cols, cols, k, idx.vp,
+              p.vp if p is not None else None, v.vp if v is not None else None)
+    return idx, p, v
+
+
 def layernorm(x: DeviceArray, g: DeviceArray, b: DeviceArray, axis: int, eps: float) -> DeviceArray:
     """model.py:134-152.  Scale and bias broadcast against x as NumPy broadcasts them."""
     outer, n, inner = _axis_split(x, axis)

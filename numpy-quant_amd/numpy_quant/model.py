@@ -85,6 +85,18 @@ def _is_image_list(array, pre) -> bool:
     return resize is not None and isinstance(array, np.ndarray) and array.dtype == np.uint8
 
 
+def _topk_output(tensor, k: int):
+    """(indices [B, k], probabilities [B, k]) device tensors of a model output [..., classes],
+    leading axes flattened into B.  A QTensor is read as it is: no float logits are made."""
+    if not isinstance(tensor, (FTensor, QTensor)) or tensor.dev.ndim < 2:
+        shape = tuple(tensor.dev.shape) if hasattr(tensor, "dev") else np.shape(getattr(tensor, "data", None))
+        raise ValueError(f"classify: the model's first output must be [batch, classes] (got {type(tensor).__name__} "
+                         f"of shape {shape})")
+    idx, prob = tensor.topk(k)
+    flat = ITensor(np.array([-1, k], dtype=np.int64))
+    return idx.reshape(flat), prob.reshape(flat)
+
+
 def _listing(kind: str, fields) -> str:
     """Readable multi-line dump of an IR object: one line per element of each list or
     dict field (the reference prints its models this way, model.py:223-234, 464-484)."""
@@ -290,8 +302,8 @@ class Model:
             else:
                 raise ValueError(f"Array dtype {array.dtype} not supported")
 
-    def __call__(self, inputs: List[np.ndarray], profile=False):
-        """Float executor (model.py:294-326), on device."""
+    def _forward(self, inputs, profile=False) -> dict:
+        """The node loop of the float executor; the outputs stay on the device."""
         times = {op: 0.0 for op in {n.op for n in self.nodes}}
         self._set_inputs(inputs)
         for node in self.nodes:
@@ -303,8 +315,22 @@ class Model:
             times[node.op] += time() - t0
             for o, tensor in zip(node.outputs, outs):
                 o.data = tensor
+        return times
+
+    def __call__(self, inputs: List[np.ndarray], profile=False):
+        """Float executor (model.py:294-326), on device."""
+        times = self._forward(inputs, profile)
         result = [out.data.data for out in self.outputs]
         return (result, times) if profile else result
+
+    def classify(self, inputs: List[np.ndarray], k: int = 5):
+        """`(indices int64 [B, k], probabilities float32 [B, k])` of the model's first output
+        [B, classes]: per row np.argsort(-logits, kind="stable")[:k] and the Softmax of the
+        logits gathered there, computed on the device (one kernel); only the [B, k] results
+        are downloaded.  Inputs as `__call__` takes them."""
+        self._forward(inputs)
+        idx, prob = _topk_output(self.outputs[0].data, k)
+        return idx.data, prob.data
 
     def calibrate(self, calibration_inputs: list[np.ndarray]) -> tuple[dict, dict]:
         """Float forward + per-value global min / max (model.py:329-336), min/max on device."""
@@ -515,7 +541,7 @@ class QModel(Model):
         out = pre.lookup_resized(slot.images(), slot.batch, slot.host.ptr, self._image_lut(variable))
         variable.data = QTensor(out, self.bit_width, scale=qp.scale, zero_point=qp.zero_point)
 
-    def classify_stream(self, batches):
+    def classify_stream(self, batches, topk=None):
         """Iterator of the model's first output for an iterable of uint8 image batches (with
         `image_preprocess.resize`: of lists of HWC images, packed with their descriptors and
         taps into the one pinned buffer), in order, equal to `qmodel([batch])[0]` of each.
@@ -523,7 +549,10 @@ class QModel(Model):
         the lookup kernel waits for its batch's copy, and a copy into a staging buffer waits
         for the kernel that last read it.  A batch the model refuses raises what
         `qmodel([batch])` raises, after the results of the batches before it were handed
-        out; the library is back on stream 0 then."""
+        out; the library is back on stream 0 then.
+        With `topk=k` it yields `(indices [B, k], probabilities [B, k])` per batch instead, equal
+        to `classify([batch], k)`: the top-k kernel is issued on the forward's stream right
+        behind it, and only its results are downloaded."""
         pre = self.image_preprocess
         if pre is None:
             raise ValueError("classify_stream: set qmodel.image_preprocess first")
@@ -553,6 +582,7 @@ class QModel(Model):
                 self._set_slot(variable, slot)
                 slot.consumed()
                 self.run(eager=self.keep_values)
+                top = None if topk is None else _topk_output(self.outputs[0].data, topk)
                 # batch k is issued: stage batch k + 1 beside it; an error of that batch is
                 # raised after batch k's result went out
                 more, failure = True, None
@@ -562,7 +592,10 @@ class QModel(Model):
                     more = False
                 except Exception as e:  # noqa: BLE001
                     failure = e
-                yield self.outputs_device()[0].data
+                if top is None:
+                    yield self.outputs_device()[0].data
+                else:
+                    yield top[0].data, top[1].data
                 if failure is not None:
                     raise failure
                 if not more:
@@ -588,11 +621,13 @@ class QModel(Model):
         from . import blob
         return blob.save(self, path)
 
-    def graph(self, example_inputs):
+    def graph(self, example_inputs, topk=None):
         """Capture one forward on inputs of this shape as a hipGraph (graph.py); the
-        returned DeviceGraph replays it with one launch and the same results."""
+        returned DeviceGraph replays it with one launch and the same results.  With
+        `topk=k` the top-k kernel is captured behind the forward and the graph returns
+        `[indices, probabilities]` as `classify(inputs, k)` does."""
         from .graph import DeviceGraph
-        return DeviceGraph(self, example_inputs)
+        return DeviceGraph(self, example_inputs, topk=topk)
 
     def _run_node(self, node, times, profile=False):
         """One iteration of the node loop of QModel.__call__ (model.py:502-550)."""
@@ -668,3 +703,18 @@ class QModel(Model):
         times = self.run(profile=profile, eager=eager)
         outs = [t.data for t in self.outputs_device()]
         return (outs, times) if profile else outs
+
+    def classify(self, inputs: List[np.ndarray], k: int = 5):
+        """`(indices int64 [B, k], probabilities float32 [B, k])` of the model's first output
+        [B, classes]: what np.argsort(-logits, kind="stable")[:, :k] and the Softmax of
+        `qmodel(inputs)[0]` gathered there give, bit for bit, computed on the device.  A
+        quantized output (the requantized classifier Gemm) is read in its integer storage by the
+        one top-k kernel: no float logits are made, and only the [B, k] results are downloaded.
+        Inputs, `image_preprocess` and the choice of the fused plan as in `__call__`."""
+        eager = self.keep_values
+        if not eager and self._plan is None and self.fuse:
+            self.compile()
+        self.set_inputs(inputs)
+        self.run(eager=eager)
+        idx, prob = _topk_output(self.outputs[0].data, k)
+        return idx.data, prob.data

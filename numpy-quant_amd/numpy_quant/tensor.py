@@ -58,6 +58,34 @@ class ITensor:
         return ITensor(self._data.take(np.atleast_1d(indices.data), axis))
 
 
+class DeviceITensor:
+    """int64 indices computed on the device (`topk`): an ITensor whose `.data` is a lazy
+    download of `.dev`, as FTensor's is."""
+
+    def __init__(self, data: DeviceArray):
+        if data.dtype != np.int64:
+            raise ValueError("Use np.int64 for index tensors")
+        self.dev = data
+        self._host = None
+
+    @property
+    def data(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self.dev.to_host()
+        return self._host
+
+    @property
+    def shape(self):
+        return ITensor(np.array(self.dev.shape, dtype=np.int64))
+
+    @property
+    def size(self):
+        return self.dev.size
+
+    def reshape(self, shape: ITensor):
+        return DeviceITensor(self.dev.reshape(_reshape_target(self.dev.shape, shape.data)))
+
+
 def _reshape_target(cur_shape, target) -> tuple[int, ...]:
     """numpy reshape target resolution (one -1 inferred, 0 is a literal 0)."""
     tgt = [int(t) for t in np.atleast_1d(np.asarray(target, dtype=np.int64))] if np.ndim(target) else [int(target)]
@@ -173,6 +201,12 @@ class FTensor:
     def softmax(self, axis: int):
         return FTensor(K.softmax(self.dev, axis))
 
+    def topk(self, k: int):
+        """(indices, probabilities) of the k largest entries of the last axis:
+        np.argsort(-x, kind="stable")[..., :k] and `softmax(-1)` gathered there, in one kernel."""
+        idx, prob, _ = K.topk_softmax(self.dev, k)
+        return DeviceITensor(idx), FTensor(prob)
+
     def sqrt(self):
         return FTensor(K.unary(_lib.SQRT, self.dev))
 
@@ -263,6 +297,14 @@ class QTensor:
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
         return FTensor(K.dequantize(self.dev, self.scale, self._zero_point))
+
+    def topk(self, k: int):
+        """`self.dequantize().topk(k)` without the float tensor: the kernel dequantizes the
+        integer storage as it reads it."""
+        if self._bias is not None:
+            raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
+        idx, prob, _ = K.topk_softmax(self.dev, k, scale=self.scale, zp=self._zero_point)
+        return DeviceITensor(idx), FTensor(prob)
 
     def requantize(self, bit_width: int, scale: np.float32, zero_point):
         bias = None
