@@ -304,6 +304,23 @@ int nqk_softmax_axis(const float* x, float* out, int64_t outer, int64_t n, int64
 int nqk_normalize_axis(const float* x, float* out, int64_t outer, int64_t n, int64_t inner, float eps);
 /* global min and max (calibration, model.py:333-336) -> out[0]=min, out[1]=max */
 int nqk_minmax_f32(const float* x, int64_t n, float* out2, float* scratch, int64_t scratch_len);
+/* Streamed calibration (calibration.py): the histogram of float32 bit patterns.
+ *   key(x) = ~bits if the sign bit is set, else bits | 0x80000000 (uint32, monotone in x over
+ *            all floats, -0.0 just before +0.0);   bin(x) = key(x) >> NQK_HIST_SHIFT.
+ * A bin is a sign, an exponent and 5 mantissa bits: 2^-5 wide relative to its values, so no
+ * range is needed in advance.
+ * state: int64 [NQK_HIST_BINS + 2] on the device: the counts, then the smallest key seen
+ * (fresh: 0xFFFFFFFF) and the largest (fresh: 0).
+ * Accumulate the key histogram and the key range of x[0..n) into state.  counts == 0: only the
+ * range entries are updated.  n == 0: nothing to do.  x needs 4-byte alignment only.  Fails
+ * before a launch on a NULL pointer, n < 0, or n > NQK_HIST_MAX_N.  Arrays of at most
+ * NQK_HIST_DIRECT_MAX elements are added straight into state; longer ones through per-workgroup
+ * histograms in LDS.  The result is the same either way, and for every order of arrival. */
+#define NQK_HIST_SHIFT 18
+#define NQK_HIST_BINS 16384
+#define NQK_HIST_DIRECT_MAX 8192 /* measured: 5.0 us straight against 6.9 us through LDS at 8 Ki, 8.5 against 6.9 at 16 Ki */
+#define NQK_HIST_MAX_N ((int64_t)1 << 40)
+int nqk_hist_f32(const float* x, int64_t n, int64_t* state, int counts);
 /* N-d strided copy for Transpose / Concat / Slice / Expand / Gather / padding
  * (element size 1, 2, 4 or 8 bytes; ndim <= 6; strides in elements) */
 int nqk_copy_strided(const void* src, void* dst, int elem_size, int ndim, const int64_t* shape,

@@ -107,6 +107,7 @@ SIGNATURES = {
     "nqk_softmax_axis": [_p, _p, _l, _l, _l],
     "nqk_normalize_axis": [_p, _p, _l, _l, _l, _f],
     "nqk_minmax_f32": [_p, _l, _p, _p, _l],
+    "nqk_hist_f32": [_p, _l, _p, _i],
     "nqk_copy_strided": [_p, _p, _i, _i, _lp, _lp, _lp],
     "nqk_where_f32": [_p, _p, _p, _p, _i, _lp, _lp, _lp, _lp],
     "nqk_pack_b": [_p, _p, _l, _l, _l],

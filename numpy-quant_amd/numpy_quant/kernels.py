@@ -591,6 +591,39 @@ def minmax(x: DeviceArray) -> tuple[np.float32, np.float32]:
     return h[0], h[1]
 
 
+HIST_SHIFT = 18                  # NQK_HIST_SHIFT: bin = key >> 18 (sign, exponent, 5 mantissa bits)
+HIST_BINS = 1 << (32 - HIST_SHIFT)  # NQK_HIST_BINS
+HIST_MAX_N = 1 << 40             # NQK_HIST_MAX_N
+# NQK_HIST_DIRECT_MAX: arrays up to this size are added straight into the state, longer ones
+# through per-workgroup LDS histograms (nqk_hist.hip).  Measured with tools/bench_calibration.py
+# (DESIGN.md §4.10): straight 3.6 us at 4 Ki elements, 5.0 at 8 Ki, 8.5 at 16 Ki and 15.6 at
+# 32 Ki; through LDS 6.8-6.9 us at each of them.  They cross near 12 Ki.
+HIST_DIRECT_MAX = 8192
+
+
+def histogram(x: DeviceArray, state: DeviceArray, counts: bool = True) -> None:
+    """Accumulate the key histogram and key range of float32 `x` into `state`, int64
+    [HIST_BINS + 2] on the device (nqk_hist_f32; calibration.py states the layout).  Asynchronous;
+    `counts=False` updates the two range entries only.  Everything is checked here, before the
+    library is touched."""
+    if not isinstance(x, DeviceArray) or not isinstance(state, DeviceArray):
+        raise ValueError("histogram: x and state must be DeviceArrays")
+    if x.dtype != np.float32:
+        raise ValueError(f"histogram: x must be float32 (got {x.dtype})")
+    if state.dtype != np.int64 or state.shape != (HIST_BINS + 2,):
+        raise ValueError(f"histogram: state must be int64 [{HIST_BINS + 2}] (got {state.dtype} {state.shape})")
+    if x.ptr % 4 or state.ptr % 8:
+        raise ValueError("histogram: x needs 4-byte and state 8-byte alignment")
+    if x.size > HIST_MAX_N:
+        raise ValueError(f"histogram: more than {HIST_MAX_N} elements")
+    for arr, what in ((x, "x"), (state, "state")):
+        if arr.ptr < arr.block.ptr or arr.ptr + arr.nbytes > arr.block.ptr + arr.block.size:
+            raise ValueError(f"histogram: {what} reaches outside its buffer")
+    if x.size == 0:
+        return
+    _lib.call("nqk_hist_f32", x.vp, x.size, state.vp, 1 if counts else 0)
+
+
 def where(cond: np.ndarray, a: DeviceArray, b: DeviceArray) -> DeviceArray:
     c = DeviceArray.from_host(np.asarray(cond).astype(np.int64))
     out_shape = tuple(np.broadcast_shapes(c.shape, a.shape, b.shape))

@@ -357,6 +357,35 @@ class Model:
 
         return self._rewrite(bit_width, params)
 
+    def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
+        """`calibrate` over any number of batches (calibration.py): per batch one float forward
+        whose values are accumulated on the device into per-value histograms of float bit
+        patterns; nothing is downloaded until the end, and only one batch's values are alive at
+        a time.  `batches`: an iterable (a generator will do: one pass) of input lists as
+        `__call__` takes them.  `percentile` in (50, 100] clips every variable's range at that
+        percentile of all its observed elements, to 2^-5 relative; 100 is the exact min / max,
+        `calibrate`'s answer.  `clip_weights`: clip the constants too."""
+        from .calibration import Calibrator
+        cal = Calibrator(percentile, clip_weights)
+        seen = False
+        for inputs in batches:
+            self._forward(inputs)
+            cal.observe(self)
+            seen = True
+        if not seen:
+            raise ValueError("calibrate_stream: no calibration batch")
+        return cal.ranges()
+
+    def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False):
+        """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`."""
+        vmin, vmax = self.calibrate_stream(batches, percentile, clip_weights)
+
+        def params(value: Value, asym: bool):
+            s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
+            return QuantizationParams(s, z)
+
+        return self._rewrite(bit_width, params)
+
     def quantize_with(self, quant_params: dict, bit_width=8):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
