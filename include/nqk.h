@@ -178,7 +178,10 @@ int nqk_image_resize_lut(const uint8_t* pixels, int64_t pixel_bytes, const void*
 /* q_matmul's integer product, numpy_quantization.py:47:
  *   C[b][m][n] = sum_k A[b'][m][k] * Bt[b''][n][k]     (int32 out)
  * int8 operands on v_mfma_i32_32x32x32_i8; lda/ldb multiples of 16 bytes; K is
- * zero-padded by the caller to a multiple of 16 (zeros add nothing). */
+ * zero-padded by the caller to a multiple of 16 (zeros add nothing).  The int32
+ * accumulator is exact while the unpadded K is below 2^17 (|a * b| <= 2^14, and
+ * 131072 products of -128 * -128 are 2^31); a padded K above 2^17 is an error, and
+ * the caller sends K >= 2^17 to nqk_qgemm_generic. */
 int nqk_qgemm_i8(const int8_t* a, const int8_t* bt, int32_t* c, int64_t batch, int64_t M,
                  int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                  const int64_t* bmap /* 5: inner, ao, ai, bo, bi in matrices */,

@@ -2,7 +2,8 @@
 //
 //  * nqk_qgemm_i8     — q_matmul's integer product (numpy_quantization.py:47) for
 //                       bit widths <= 8 on v_mfma_i32_32x32x32_i8.  int32
-//                       accumulation is exact: |a|,|b| <= 128, K < 2^17.
+//                       accumulation is exact: |a|,|b| <= 128, K < 2^17 (the caller
+//                       routes longer K to nqk_qgemm_generic, kernels.I8_MAX_K).
 //  * nqk_qgemm_generic — the same product for any storage width, int64 on VALU
 //                       (bit widths 9..32, tiny shapes such as the MLP).
 //  * nqk_sgemm        — float32 GEMM that reproduces the reference BLAS bit for
@@ -1168,6 +1169,8 @@ extern "C" int nqk_qgemm_i8(const int8_t* a, const int8_t* bt, int32_t* c, int64
   if ((((uintptr_t)a) & 15) || (((uintptr_t)bt) & 15) || (a_mat_stride & 15) || (b_mat_stride & 15))
     return fail("nqk_qgemm_i8: operands must be 16-byte aligned");
   if (batch > 65535) return fail("nqk_qgemm_i8: batch > 65535");
+  // 2^17 products of magnitude 2^14 reach 2^31; the padded K of a safe product is at most 2^17
+  if (K > (1 << 17)) return fail("nqk_qgemm_i8: K above 131072 can overflow the int32 accumulator (use nqk_qgemm_generic)");
   int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
   if ((int64_t)tiles_m * tiles_n > 0x7fffffff) return fail("nqk_qgemm_i8: too many tiles");
   BatchMap m = batch_map(bmap);

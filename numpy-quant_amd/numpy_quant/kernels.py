@@ -29,14 +29,35 @@ def storage_dtype(bit_width: int) -> np.dtype:
     return np.dtype(np.int64)
 
 
+def _f32_bound_exceeds(bit_width: int, zp) -> bool:
+    """Without a zero point the reference clips in float32, and float32(2^31 - 1) is 2^31: at
+    bit width 32 the upper bound itself does not fit the int32 storage of that width.  (For
+    25..31 bits the rounded bound 2^(bw-1) still fits; with a zero point the clip is in
+    float64 and exact.)"""
+    return zp is None and bit_width == 32
+
+
+def _narrow_if_fits(q: DeviceArray, dt: np.dtype) -> DeviceArray:
+    """An int64 result in storage `dt` when every value fits it, else as it is.  One download
+    and one upload: this runs for biases when a model is built, not per forward."""
+    h = q.to_host()
+    info = np.iinfo(dt)
+    if h.size and (h.min() < info.min or h.max() > info.max):
+        return q
+    return DeviceArray.from_host(h.astype(dt))
+
+
 # ----------------------------------------------------------------------------- quantization
 def quantize(x: DeviceArray, bit_width: int, scale: float, zp: int | None, out_dtype=None,
              rowsum: bool = False):
-    """numpy_quantization.py:24-34 on device.  Returns (q, rowsum | None)."""
+    """numpy_quantization.py:24-34 on device.  Returns (q, rowsum | None).  Storage is
+    `out_dtype`, else `storage_dtype(bit_width)`; the one exception is bit width 32 without a
+    zero point, whose saturated value +2^31 needs int64 (int32 whenever nothing saturates)."""
     if x.dtype != np.float32:
         raise ValueError("quantize expects float32 input")
     dt = np.dtype(out_dtype) if out_dtype is not None else storage_dtype(bit_width)
-    q = DeviceArray(x.shape, dt)
+    widen = out_dtype is None and _f32_bound_exceeds(bit_width, zp)
+    q = DeviceArray(x.shape, np.int64 if widen else dt)
     rs = None
     row_len = x.shape[-1] if x.ndim else 1
     if rowsum:
@@ -44,6 +65,8 @@ def quantize(x: DeviceArray, bit_width: int, scale: float, zp: int | None, out_d
     _lib.call("nqk_quantize", x.vp, q.vp, q.code, x.size, float(np.float32(scale)),
               0 if zp is None else int(zp), 0 if zp is None else 1, int(bit_width),
               rs.vp if rs is not None else None, row_len)
+    if widen:
+        q = _narrow_if_fits(q, dt)
     return q, rs
 
 
@@ -102,8 +125,11 @@ def dequantize(q: DeviceArray, scale, zp) -> DeviceArray:
 
 def requantize(acc: DeviceArray, scale, zp, bias: DeviceArray | None, res_scale, res_zp,
                bit_width: int) -> DeviceArray:
-    """numpy_quantization.py:64-72 with the Gemm bias add (tensor.py:255-259) fused."""
-    out = DeviceArray(acc.shape, storage_dtype(bit_width))
+    """numpy_quantization.py:64-72 with the Gemm bias add (tensor.py:255-259) fused.  Storage as
+    for `quantize`: int64 at bit width 32 without a result zero point where +2^31 occurs."""
+    dt = storage_dtype(bit_width)
+    widen = _f32_bound_exceeds(bit_width, res_zp)
+    out = DeviceArray(acc.shape, np.int64 if widen else dt)
     flags, z, zpa, zpb, K, row, col, bmap = _zp_args(zp)
     b, m, n = _bmn(acc.shape) if acc.ndim >= 2 else (1, 1, acc.size)
     if bias is not None and bias.size != n:
@@ -113,7 +139,7 @@ def requantize(acc: DeviceArray, scale, zp, bias: DeviceArray | None, res_scale,
               float(np.float32(scale)), flags, z, zpa, zpb, K, row, col, bmap,
               float(np.float32(res_scale)), 0 if res_zp is None else int(res_zp),
               0 if res_zp is None else 1, int(bit_width))
-    return out
+    return _narrow_if_fits(out, dt) if widen else out
 
 
 def rowsum(a: DeviceArray, batch: int, rows: int, k: int, ld: int, bstride: int) -> DeviceArray:
@@ -159,6 +185,9 @@ def batch_map(a_batch, b_batch):
 
 # ----------------------------------------------------------------------------- integer GEMM
 MFMA_MIN_WORK = 1 << 15
+# nqk_qgemm_i8 accumulates in int32: |a * b| <= 2^14, so K products stay below 2^31 only while
+# K < 2^17 (K = 131072 of -128 * -128 is exactly 2^31).  Longer K goes to the int64 kernel.
+I8_MAX_K = 1 << 17
 
 
 class KernelTimer:
@@ -235,7 +264,8 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
         _, bmap = batch_map(a_batch, b_batch)
     nb = int(math.prod(out_batch))
     na, nbb = int(math.prod(a_batch)), int(math.prod(b_batch))
-    use_mfma = (a.dtype == np.int8 and b.dtype == np.int8 and M * N * K >= MFMA_MIN_WORK and nb <= 65535)
+    use_mfma = (a.dtype == np.int8 and b.dtype == np.int8 and M * N * K >= MFMA_MIN_WORK and nb <= 65535
+                and K < I8_MAX_K)
     if use_mfma:
         kp = (K + 15) // 16 * 16
         ap = a if K == kp else _pad_k(a, a.shape[:-1], K, kp)
