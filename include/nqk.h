@@ -451,9 +451,12 @@ int nqk_transpose_pad_i8(const int8_t* src, int8_t* dst, int64_t* rowsum, int64_
  * softmax, numpy_quantization.py:24-61 quantize / q_matmul), bit-identical to
  * nqk_qgemm_fused(SCORES) + nqk_softmax_quant + nqk_qgemm_fused(PV).
  * q, k, v: int8 [batch_heads][tokens][64]; ctx: int8 [batch_heads / heads][tokens][ld_out],
- * head h at columns h*64.  tokens <= 224; |zq|,|zk| <= 4096, |zp_p|,|zv| <= 1024. */
+ * head h at columns h*64.  tokens <= 224; |zq|,|zk| <= 4096, |zp_p|,|zv| <= 1024.
+ * q_rows: 0 computes every query row; 0 < q_rows <= tokens computes and stores only the query
+ * rows m < q_rows of every (image, head), with the bytes the full call writes there, and leaves
+ * the other rows of ctx untouched (K and V are read whole).  Other values are refused. */
 typedef struct nqk_attention {
-  int32_t heads, tokens, hdim, ld_out, bit_width, pad0;
+  int32_t heads, tokens, hdim, ld_out, bit_width, q_rows;
   int64_t zq, zk;          /* zero points of the quantized Q and K^T                 */
   float s_qk, div;         /* f32(s_q * s_k), the scores Div constant                */
   float s_p, s_pv;         /* softmax-output scale, f32(s_p * s_v)                   */

@@ -91,6 +91,7 @@ struct AttnArgs {
   double rdiv, rs_p, zp_p, rs_ctx, zp_ctx, lo, hi;
   float inv_div, rs_ctx_f, zp_p_f, zp_ctx_f, lo_f, hi_f;  // FAST path constants
   float s_qkd;  // s_qk / div (div a power of two, s_qk / div in [2^-100, 2^100]: exact)
+  int QR;       // query rows computed and stored: rows m < QR (nqk_attention.q_rows; T when that is 0)
 };
 
 __device__ __forceinline__ int swz64a(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
@@ -335,7 +336,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
               packed = (packed & ~(0xffu << (8 * jj))) | ((uint32_t)(qv & 0xff) << (8 * jj));
             }
           }
-          if (m < T) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
+          if (m < a.QR) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
           __builtin_amdgcn_sched_barrier(0);
           continue;
         } else {
@@ -344,11 +345,14 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
         }
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) packed |= ((uint32_t)(qs[jj] & 0xff)) << (8 * jj);
-        if (m < T) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
+        if (m < a.QR) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
         __builtin_amdgcn_sched_barrier(0);
       }
   };
-  for (int rt = wave; rt < (TAILR ? NT - 1 : NT); rt += 4) {
+  // a prefix of the query rows (a.QR < T): only the row tiles that hold one; a wave without a tile
+  // has helped stage K / V and is done
+  const int ntq = (a.QR + 31) >> 5;
+  for (int rt = wave; rt < (TAILR ? min(ntq, NT - 1) : ntq); rt += 4) {
     const int m0 = rt * 32, m = m0 + r32;
     v4i qb[2];
     const int nrowterm = q_rows(m, qb);
@@ -779,7 +783,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
     ctx_store(m, rp, acc2);
   }
   if constexpr (TAILR) {
-    if (wave == (NT - 1) % 4) {
+    if (wave == (NT - 1) % 4 && ntq == NT) {
       const int rt = NT - 1, m = rt * 32 + r32;
       v4i qb[2];
       const int nrowterm = q_rows(m, qb);
@@ -1088,8 +1092,11 @@ k_attn16(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int
     const int mq = rt * 16 + l15;
     return *reinterpret_cast<const v4i*>(q + (mq < T ? mq : T - 1) * 64 + g * 16);
   };
+  // a prefix of the query rows (a.QR < T): only the row tiles that hold one; a wave without a tile
+  // has helped stage K / V and is done
+  const int ntq = (a.QR + 15) >> 4;
   v4i qnext = q_frag(wave);  // NQK_ATTN16_QPF: the next row tile's Q fragment loads under this one's work
-  for (int rt = wave; rt < NT; rt += NW) {
+  for (int rt = wave; rt < ntq; rt += NW) {
     const int m = rt * 16 + l15;  // the lane's query row
     const v4i qb = NQK_ATTN16_QPF ? qnext : q_frag(rt);
     int nrowterm;
@@ -1125,7 +1132,7 @@ k_attn16(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int
         e[c][r + 1] = y[1];
       }
     }
-    if (NQK_ATTN16_QPF && rt + NW < NT) qnext = q_frag(rt + NW);
+    if (NQK_ATTN16_QPF && rt + NW < ntq) qnext = q_frag(rt + NW);
     mx = __builtin_fmaxf(mx, (float)imx * a.s_qkd);
     mx = __builtin_fmaxf(mx, xor16f(mx));
     mx = __builtin_fmaxf(mx, xor32f(mx));
@@ -1287,7 +1294,7 @@ k_attn16(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int
           packed = (packed & ~(0xffu << (8 * jj))) | ((uint32_t)(qv & 0xff) << (8 * jj));
         }
       }
-      if (m < T) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
+      if (m < a.QR) *reinterpret_cast<uint32_t*>(orow + d0) = packed;
     }
   }
 }
@@ -1302,6 +1309,7 @@ extern "C" int nqk_attention_fused(const int8_t* q, const int8_t* k, const int8_
   const int T = p->tokens;
   if (p->hdim != 64) return fail("nqk_attention_fused: head dimension 64 expected");
   if (T < 1 || T > 224) return fail("nqk_attention_fused: 1 <= tokens <= 224 expected");
+  if (p->q_rows < 0 || p->q_rows > T) return fail("nqk_attention_fused: 0 <= q_rows <= tokens expected");
   if (p->heads < 1 || batch_heads % p->heads) return fail("nqk_attention_fused: batch_heads % heads != 0");
   if (p->ld_out < p->heads * 64) return fail("nqk_attention_fused: ld_out < heads * 64");
   if (p->bit_width < 2 || p->bit_width > 8) return fail("nqk_attention_fused: 2 <= bit_width <= 8 expected");
@@ -1317,6 +1325,7 @@ extern "C" int nqk_attention_fused(const int8_t* q, const int8_t* k, const int8_
   const int NT = (T + 31) / 32;
   AttnArgs a{};
   a.T = T;
+  a.QR = p->q_rows ? p->q_rows : T;
   a.H = p->heads;
   a.ld_out = p->ld_out;
   int est = (T + 3) / 4 * 4;

@@ -44,7 +44,7 @@ class Epilogue(ctypes.Structure):
 class Attention(ctypes.Structure):
     """Mirror of `nqk_attention` (include/nqk.h)."""
     _fields_ = [("heads", ctypes.c_int32), ("tokens", ctypes.c_int32), ("hdim", ctypes.c_int32),
-                ("ld_out", ctypes.c_int32), ("bit_width", ctypes.c_int32), ("pad0", ctypes.c_int32),
+                ("ld_out", ctypes.c_int32), ("bit_width", ctypes.c_int32), ("q_rows", ctypes.c_int32),
                 ("zq", ctypes.c_int64), ("zk", ctypes.c_int64),
                 ("s_qk", ctypes.c_float), ("div", ctypes.c_float), ("s_p", ctypes.c_float), ("s_pv", ctypes.c_float),
                 ("zp_p", ctypes.c_int64), ("zv", ctypes.c_int64),

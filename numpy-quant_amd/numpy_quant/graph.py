@@ -60,6 +60,11 @@ class DeviceGraph:
         if qmodel._plan is not None or (qmodel.fuse and not qmodel.keep_values):
             from .plan import compile_plan
             self.plan = compile_plan(qmodel)
+            # a replay returns outputs only: a cls_tail layer's output value is FusedAway here, not
+            # a DeferredRows whose read would run kernels on buffers the next replay overwrites
+            for kind, step in self.plan.steps:
+                if kind == "layer":
+                    step.keep_deferred = False
         self.exec = ctypes.c_void_p()
         self.outs: list = []  # FTensors; with topk [DeviceITensor, FTensor]
         self.blocks = []

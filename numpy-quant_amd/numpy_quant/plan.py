@@ -570,16 +570,63 @@ class LnGather:
         if ax != -1 or gax in (-1,):
             raise NoMatch("LN over the last axis, Gather over another one")
         self.ln, self.g, self.nodes = ln, g, {ln, g}
+        self.cls_layer = None  # the cls_tail FusedLayer that computes only the gathered rows (Plan)
+
+    def gathers_token0(self) -> bool:
+        """Whether the Gather reads token 0 alone of a [B, T, D] input: axis 1, one constant
+        index (a scalar or a one-element array) equal to 0."""
+        idx = np.asarray(_const_node_value(self.g.inputs[1])[0])
+        return int(self.g.attrs.get("axis", 0)) == 1 and idx.size == 1 and int(idx.reshape(-1)[0]) == 0
 
     def run(self, qmodel, times=None, profile=False):
         from .model import onnx_operator_implementation
-        x = self.ln.inputs[0].data
-        if not isinstance(x, FTensor) or int(self.g.attrs.get("axis", 0)) % x.dev.ndim == x.dev.ndim - 1:
-            raise ValueError("LN/Gather pushdown needs a float input gathered off the last axis")
-        xs = x.take(self.g.inputs[1].data, axis=int(self.g.attrs.get("axis", 0)))
+        if self.cls_layer is not None:
+            # the layer in front computed the gathered rows only: its compact [B, 1, D] output,
+            # in the Gather's output shape
+            c = self.cls_layer.cls_out.dev
+            idx = np.asarray(self.g.inputs[1].data.data)
+            xs = FTensor(c.reshape((c.shape[0],) + idx.shape + (c.shape[2],)))
+        else:
+            xs = self._gather()
         args = [xs] + [qmodel._dequant_input(v) if isinstance(v.data, QTensor) else v.data for v in self.ln.inputs[1:]]
         self.g.outputs[0].data = onnx_operator_implementation("LayerNormalization", args, self.ln.attrs)[0]
         self.ln.outputs[0].data = FusedAway(self.ln.outputs[0].name)
+
+    def _gather(self):
+        x = self.ln.inputs[0].data
+        if not isinstance(x, FTensor) or int(self.g.attrs.get("axis", 0)) % x.dev.ndim == x.dev.ndim - 1:
+            raise ValueError("LN/Gather pushdown needs a float input gathered off the last axis")
+        return x.take(self.g.inputs[1].data, axis=int(self.g.attrs.get("axis", 0)))
+
+
+class DeferredRows(FTensor):
+    """The output value of a cls_tail layer: the run computed only its token-0 rows.  The first read
+    of `.dev` (or `.data`) computes every row (FusedLayer._all_rows: the unpruned steps from the
+    attention on, whole batch on stream 0, from the run's q / k / v and layer input, which the
+    tensor holds) and from then on it is an ordinary FTensor.  The plan's next run writes the
+    workspace again: a tensor not read by then raises as a FusedAway value does."""
+
+    def __init__(self, name, shape, thunk):
+        self.name, self._shape, self._thunk = name, tuple(shape), thunk
+        self._dev = self._host = None
+
+    @property
+    def dev(self):
+        if self._dev is None:
+            if self._thunk is None:
+                raise FusedAwayError(f"value {self.name!r}: only its token-0 rows were computed, and a later run "
+                                     "has reused the layer's workspace; read it before the next run, or set "
+                                     "QModel.keep_values = True")
+            self._dev, self._thunk = self._thunk(), None
+        return self._dev
+
+    @property
+    def shape(self):
+        from .tensor import ITensor
+        return ITensor(np.array(self._shape, dtype=np.int64))
+
+    def expire(self):
+        self._thunk = None
 
 
 # ----------------------------------------------------------------------------- fused layer
@@ -655,6 +702,13 @@ class FusedLayer:
         self.ln_fuse = self.D == 192 and not os.environ.get("NQK_NO_LNFUSE")
         self.next_ln = None        # the next fused layer, whose LN1 this layer's FFN-down computes
         self.ln1_by_prev = False   # this layer's LN1 is computed by the previous layer's FFN-down
+        # set by the Plan: the layer's output feeds only a LayerNorm whose Gather reads token 0, so
+        # after K and V only the token-0 rows are computed (run); cls_out is then the run's compact
+        # [B, 1, D] output, and the output value a DeferredRows (keep_deferred) or FusedAway
+        self.cls_tail = False
+        self.keep_deferred = True
+        self.cls_out = None
+        self.deferred = None
 
     def _epi(self, **kw) -> Epilogue:
         e = Epilogue()
@@ -723,6 +777,9 @@ class FusedLayer:
         H, Dh, F = m.heads, m.hdim, self.F
         Tp = (T + 15) // 16 * 16
         w = ws.get(B, T, Tp, H, Dh, D, F, unfused_attention=not self.attn_fused)
+        if self.cls_tail:
+            self._run_cls(ws, w, x, B, streams)
+            return
         # x1 is layer-private scratch shared by all layers (halves touch disjoint rows);
         # x2 is the layer's output value
         x2 = DeviceArray((B, T, D), np.float32)
@@ -732,10 +789,53 @@ class FusedLayer:
         streams.halves(B, lambda s_idx, i0, nb: self._run_part(w, x.dev, w["x1"], x2, i0, nb, s_idx, streams.parts))
         m.x_out.data = FTensor(x2)
 
-    def _run_part(self, w, xd, x1d, x2d, i0, nb, s_idx=0, parts=1):
+    def _run_cls(self, ws, w, x, B, streams):
+        """The cls_tail layer: LN1, QKV and the attention of query row 0 per part on the streams as
+        ever; then token 0's context row (int8) and layer-input row (f32) of every image, gathered
+        into compact [B, D] buffers (nqk_copy_strided), go through the out-projection, LN2 and the
+        FFN as M = images dense rows, still per part on its stream (B = 256: two M = 128 tails; one
+        whole-batch tail on stream 0 after a join measured the same).  The same GEMM /
+        LayerNorm calls, epilogue parameters and weight images as the full layer (only a width-192
+        layer's LN2 is its own launch here)."""
+        from .device import copy_strided
+        m = self.m
+        T, D = m.tokens, self.D
+        c = ws.cls(B, D, self.F)
+        out = DeviceArray((B, 1, D), np.float32)
+
+        def part(s_idx, i0, nb):
+            def rows(arr):
+                ncol = arr.shape[-1]
+                return arr.offset_view(i0 * ncol, (nb, ncol))
+            self._run_part(w, x.dev, None, None, i0, nb, s_idx, streams.parts, q_rows=1)
+            copy_strided(w["ctx"], c["ctx"], (nb, D), (T * D, 1), (D, 1), i0 * T * D, i0 * D)
+            copy_strided(x.dev, c["x"], (nb, D), (T * D, 1), (D, 1), i0 * T * D, i0 * D)
+            self._back(rows(c["x"]), rows(c["ctx"]), rows(c["x1"]), rows(c["ln2q"]), rows(c["h"]),
+                       rows(out.reshape((B, D))), None, nb, ln_fuse=False)
+
+        streams.halves(B, part)
+        self.cls_out = FTensor(out)
+        if self.keep_deferred:
+            self.deferred = DeferredRows(m.x_out.name, (B, T, D), lambda: self._all_rows(w, x, B))
+            m.x_out.data = self.deferred
+        else:
+            m.x_out.data = FusedAway(m.x_out.name)
+
+    def _all_rows(self, w, x, B):
+        """Every row of a cls_tail layer's output, after its run: the unpruned steps from the attention
+        on, whole batch on stream 0 (q, k, v in the workspace w and the layer input x are the run's)."""
+        _lib.call("nqk_set_stream", 0)
+        _lib.call("nqk_stream_join")
+        x2 = DeviceArray((B, self.m.tokens, self.D), np.float32)
+        self._run_part(w, x.dev, w["x1"], x2, 0, B, front=False)
+        return x2
+
+    def _run_part(self, w, xd, x1d, x2d, i0, nb, s_idx=0, parts=1, q_rows=0, front=True):
         """Images [i0, i0 + nb) of the layer (row views of every buffer).  NQK_STREAM_LAG
         (ln1 / qkv / attn): part s > 0 starts the layer only after part s - 1 has finished that
-        kernel of it, so the parts' kernels of different kinds run side by side (A/B switch)."""
+        kernel of it, so the parts' kernels of different kinds run side by side (A/B switch).
+        q_rows > 0: LN1, QKV and the attention of the first q_rows query rows only (the cls_tail
+        layer's front); front = False: the attention and everything after it, from q / k / v."""
         m, bw = self.m, self.bw
         lag = _stream_lag() if parts > 1 else None
         if lag and s_idx > 0:
@@ -753,31 +853,32 @@ class FusedLayer:
         def rows(arr, ncol):
             return arr.offset_view(r0 * ncol, (Mrows, ncol))
 
-        x, x1, x2 = (rows(t.reshape((t.size // D, D)), D) for t in (xd, x1d, x2d))
+        x = rows(xd.reshape((xd.size // D, D)), D)
         lnq, ln2q, ctx, hh = rows(w["lnq"], D), rows(w["ln2q"], D), rows(w["ctx"], D), rows(w["h"], F)
         hq = i0 * H * T * Dh  # head-layout offset of the first image
         q, k, v = (w[r].offset_view(hq, (nb * H * T, Dh)) for r in "qkv")
         call = _lib.call
-        # 1) LN1 + quantize (LN1 output feeds the Q/K/V MatMuls; already in lnq when the previous
-        # layer's FFN-down epilogue computed it)
-        if not self.ln1_by_prev:
-            _ln_quant(x, self.g1, self.be1, lnq, Mrows, D, self.eps1, self.p_ln1, bw)
-        mark("ln1")
-        # 2) QKV projection: dequant + bias + head split + quantize with each head consumer's params
-        s_a = np.float32(self.p_ln1.scale)
-        e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln1), group_cols=D, col=self.col_qkv.ptr,
-                      col_absmax=self.cmax["qkv"], col_l1max=self.l1max["qkv"], colterm=_ptr(self.ct["qkv"]),
-                      s_acc=[_f32(s_a * np.float32(self.s_w[r])) for r in "qkv"],
-                      s_out=[_f32(self.p_head[r].scale) for r in "qkv"],
-                      zp_out=[_zp(self.p_head[r]) for r in "qkv"],
-                      out=[q.ptr, k.ptr, v.ptr], bias=self.bias_qkv.ptr)
-        _gemm(EPI_QKV, lnq, self._b(e, "qkv", self.bt_qkv), 1, Mrows, 3 * D, D, D, D, None, 0, 0, e)
-        mark("qkv")
+        if front:
+            # 1) LN1 + quantize (LN1 output feeds the Q/K/V MatMuls; already in lnq when the previous
+            # layer's FFN-down epilogue computed it)
+            if not self.ln1_by_prev:
+                _ln_quant(x, self.g1, self.be1, lnq, Mrows, D, self.eps1, self.p_ln1, bw)
+            mark("ln1")
+            # 2) QKV projection: dequant + bias + head split + quantize with each head consumer's params
+            s_a = np.float32(self.p_ln1.scale)
+            e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln1), group_cols=D, col=self.col_qkv.ptr,
+                          col_absmax=self.cmax["qkv"], col_l1max=self.l1max["qkv"], colterm=_ptr(self.ct["qkv"]),
+                          s_acc=[_f32(s_a * np.float32(self.s_w[r])) for r in "qkv"],
+                          s_out=[_f32(self.p_head[r].scale) for r in "qkv"],
+                          zp_out=[_zp(self.p_head[r]) for r in "qkv"],
+                          out=[q.ptr, k.ptr, v.ptr], bias=self.bias_qkv.ptr)
+            _gemm(EPI_QKV, lnq, self._b(e, "qkv", self.bt_qkv), 1, Mrows, 3 * D, D, D, D, None, 0, 0, e)
+            mark("qkv")
         pq, pk, pv_ = self.p_head["q"], self.p_head["k"], self.p_head["v"]
         if self.attn_fused:
             # 3-6) one kernel per (image, head): scores, softmax, P V, context quantize
             a = _lib.Attention()
-            a.heads, a.tokens, a.hdim, a.ld_out, a.bit_width = H, T, Dh, D, bw
+            a.heads, a.tokens, a.hdim, a.ld_out, a.bit_width, a.q_rows = H, T, Dh, D, bw, q_rows
             a.zq, a.zk = _zp(pq), _zp(pk)
             a.s_qk, a.div = _f32(np.float32(pq.scale) * np.float32(pk.scale)), m.div
             a.s_p, a.zp_p = _f32(self.p_sm.scale), _zp(self.p_sm)
@@ -786,19 +887,30 @@ class FusedLayer:
             t0 = KM.TIMER.begin() if KM.TIMER is not None else None
             call("nqk_attention_fused", q.vp, k.vp, v.vp, ctx.vp, nb * H, ctypes.byref(a))
             if t0 is not None:
-                KM.TIMER.end("attention", t0, (2 * 2 * nb * H * T * T * Dh, 3 * nb * H * T * Dh + nb * T * D))
+                qr = q_rows or T  # the query rows computed: K and V are read whole
+                KM.TIMER.end("attention", t0, (2 * 2 * nb * H * qr * T * Dh, nb * H * Dh * (qr + 2 * T) + nb * qr * D))
         else:
             self._attention_unfused(w, nb, T, Tp, H, Dh, D)  # whole batch only (i0 == 0)
         mark("attn")
+        if q_rows:
+            return
+        x1, x2 = (rows(t.reshape((t.size // D, D)), D) for t in (x1d, x2d))
+        self._back(x, ctx, x1, ln2q, hh, x2, lnq, Mrows, self.ln_fuse)
+
+    def _back(self, x, ctx, x1, ln2q, hh, x2, lnq, Mrows, ln_fuse):
+        """Steps 7-10 on Mrows dense rows: the layer input x and context ctx to the output x2 (x1,
+        ln2q, hh: scratch rows)."""
+        m, bw = self.m, self.bw
+        D, F = self.D, self.F
         # 7) output projection + bias + residual
         e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ctx), col=self.col_o.ptr, col_absmax=self.cmax["o"], col_l1max=self.l1max["o"],
                       colterm=_ptr(self.ct["o"]),
                       s_acc=[_f32(np.float32(self.p_ctx.scale) * np.float32(self.s_wo))], bias=self.bias_o.ptr,
                       resid=x.ptr, out=[x1.ptr])
-        if self.ln_fuse:  # 8) LN2 + quantize inside the epilogue
+        if ln_fuse:  # 8) LN2 + quantize inside the epilogue
             self._ln_into(e, self.g2, self.be2, self.eps2, self.p_ln2, ln2q)
         _gemm(EPI_RESID, ctx, self._b(e, "o", self.bt_o), 1, Mrows, D, D, D, D, None, 0, 0, e)
-        if not self.ln_fuse:  # 8) LN2 + quantize
+        if not ln_fuse:  # 8) LN2 + quantize
             _ln_quant(x1, self.g2, self.be2, ln2q, Mrows, D, self.eps2, self.p_ln2, bw)
         # 9) FFN up + bias + GELU + quantize
         e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln2), col=self.col_1.ptr, col_absmax=self.cmax["1"], col_l1max=self.l1max["1"],
@@ -947,6 +1059,8 @@ class Workspace:
     def __init__(self):
         self.key = None
         self.bufs = {}
+        self.cls_key = None
+        self.cls_bufs = {}
 
     def get(self, B, T, Tp, H, Dh, D, F, unfused_attention=True):
         key = (B, T, Tp, H, Dh, D, F)
@@ -966,6 +1080,16 @@ class Workspace:
                               "s": DeviceArray((B * H, T, T), np.float32),
                               "p": DeviceArray((B * H, T, Tp), np.int8)})
         return self.bufs
+
+    def cls(self, B, D, F):
+        """The compact rows of a cls_tail layer (one per image): gathered layer input and context,
+        and the tail's scratch rows."""
+        if self.cls_key != (B, D, F):
+            self.cls_bufs = {"x": DeviceArray((B, D), np.float32), "ctx": DeviceArray((B, D), np.int8),
+                             "x1": DeviceArray((B, D), np.float32), "ln2q": DeviceArray((B, D), np.int8),
+                             "h": DeviceArray((B, F), np.int8)}
+            self.cls_key = (B, D, F)
+        return self.cls_bufs
 
 
 class FusedAwayError(RuntimeError):
@@ -1067,6 +1191,19 @@ class Plan:
                     (a.D, a.F, a.m.heads, a.m.hdim, a.m.tokens, a.attn_fused) ==
                     (b.D, b.F, b.m.heads, b.m.hdim, b.m.tokens, b.attn_fused)):
                 a.next_ln, b.ln1_by_prev = b, True
+        # a fused layer (one-kernel attention) whose output is read only by the LayerNorm of an
+        # LnGather that gathers token 0, and is no graph output: after K and V, every operation of
+        # the layer is row-wise, so only the token-0 rows are computed (FusedLayer._run_cls).
+        # NQK_NO_CLS_TAIL=1 keeps the full layer.
+        self.cls_tails = 0
+        if not os.environ.get("NQK_NO_CLS_TAIL"):
+            layers = {id(l.m.x_out): l for k, l in self.steps if k == "layer"}
+            for k, lg in self.steps:
+                layer = layers.get(id(lg.ln.inputs[0])) if k == "ln_gather" else None
+                if (layer is not None and layer.attn_fused and len(layer.m.x_out.outputs) == 1 and
+                        not any(layer.m.x_out is o for o in qmodel.outputs) and lg.gathers_token0()):
+                    layer.cls_tail, lg.cls_layer = True, layer
+                    self.cls_tails += 1
         # every value a fused step computes; each run first marks them all FusedAway, so that
         # no tensor of an earlier run (eager, keep_values) can be read as if it were this
         # run's; the steps then set the values their consumers outside the step read
@@ -1076,6 +1213,10 @@ class Plan:
         streams = Streams(self.split, int(os.environ.get("NQK_STREAMS", "2")))
         for v in self.internal:
             v.data = FusedAway(v.name)
+        for kind, obj in self.steps:  # this run reuses the workspace an unread DeferredRows would read
+            if kind == "layer" and obj.deferred is not None:
+                obj.deferred.expire()
+                obj.deferred = None
         try:
             for kind, obj in self.steps:
                 if kind == "node":
