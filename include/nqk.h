@@ -324,6 +324,31 @@ int nqk_minmax_f32(const float* x, int64_t n, float* out2, float* scratch, int64
 #define NQK_HIST_DIRECT_MAX 8192 /* measured: 5.0 us straight against 6.9 us through LDS at 8 Ki, 8.5 against 6.9 at 16 Ki */
 #define NQK_HIST_MAX_N ((int64_t)1 << 40)
 int nqk_hist_f32(const float* x, int64_t n, int64_t* state, int counts);
+/* Error statistics of a quantized model's value y against the float model's x (compare.py).
+ * x is f32; y is f32 (scale, zp, has_zp ignored) or integer storage NQK_I8 .. NQK_I64 read as
+ * f32(f64(q - zp) * f64(scale)), nqk_dequantize's expression with a scalar (has_zp) or no zero
+ * point, which is never written anywhere.
+ * state: 8 device words of 8 bytes, a fresh one all zero bytes, into which every call accumulates:
+ *   [0] int64 pairs compared     [1] int64 pairs skipped: x or the f32 y NaN or +-inf
+ *   [2] f64 sum |d|              [3] f64 sum d * d        [4] f64 sum f64(x) * f64(x)
+ *   [5] f64 max |d|              [6], [7] reserved, stay 0
+ * with d = f64(x) - f64(y) over the compared pairs.
+ * The sums are f64 additions in one fixed order, whatever the grid (NQK_CMP_GRID=<workgroups>,
+ * read on every call, sets that of the first launch), the CU count or the order of arrival:
+ *   chunk c = elements [NQK_CMP_CHUNK c, NQK_CMP_CHUNK (c + 1)); lane t of 256 adds the terms
+ *   of elements 4096 c + 1024 j + 4 t + k (j = 0..3 outer, k = 0..3 inner) to +0.0, absent and
+ *   skipped elements adding nothing; the 256 lane sums fold by adjacent pairs (v = v[0::2] +
+ *   v[1::2] until one is left) into scratch[s * chunks + c], s = 0, 1, 2 for the three sums;
+ *   then, one workgroup per sum: lane t adds the partials of chunks t, t + 256, .. in increasing
+ *   order to +0.0, the 256 lane sums fold the same way, and the total is added to the state word.
+ * n == 0: nothing to do.  x and y need the alignment of their elements only, state and scratch
+ * 8 bytes.  Fails before a launch on a NULL pointer, n < 0, n > NQK_CMP_MAX_N, an unknown
+ * dtype, a misaligned pointer, or scratch_len (in doubles) < 3 * ceil(n / NQK_CMP_CHUNK). */
+#define NQK_CMP_STATE 8
+#define NQK_CMP_CHUNK 4096
+#define NQK_CMP_MAX_N ((int64_t)1 << 36)
+int nqk_compare_stats(const float* x, const void* y, int y_dtype, float scale, int64_t zp, int has_zp,
+                      int64_t n, int64_t* state, double* scratch, int64_t scratch_len);
 /* N-d strided copy for Transpose / Concat / Slice / Expand / Gather / padding
  * (element size 1, 2, 4 or 8 bytes; ndim <= 6; strides in elements) */
 int nqk_copy_strided(const void* src, void* dst, int elem_size, int ndim, const int64_t* shape,

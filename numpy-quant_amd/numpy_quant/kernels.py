@@ -654,6 +654,53 @@ def histogram(x: DeviceArray, state: DeviceArray, counts: bool = True) -> None:
     _lib.call("nqk_hist_f32", x.vp, x.size, state.vp, 1 if counts else 0)
 
 
+CMP_STATE = 8            # NQK_CMP_STATE: words of a comparison state
+CMP_CHUNK = 4096         # NQK_CMP_CHUNK: elements per chunk partial
+CMP_MAX_N = 1 << 36      # NQK_CMP_MAX_N
+
+
+def compare_stats(x: DeviceArray, y: DeviceArray, state: DeviceArray, scale=None, zp=None) -> None:
+    """Accumulate the error statistics of `y` against float32 `x` into `state`, int64 [CMP_STATE]
+    on the device (nqk_compare_stats; compare.py states the layout and the order of the sums).
+    y is float32 (scale and zp stay None) or the integer storage of a QTensor with its `scale`
+    and scalar (or no) zero point, read as `dequantize(y, scale, zp)` without materialising it.
+    Asynchronous.  Every argument is checked here, before the library is touched."""
+    if isinstance(zp, ZpTerm):
+        raise ValueError("compare_stats: a q_matmul zero-point term (ZpTerm) is not supported; dequantize first")
+    if not all(isinstance(a, DeviceArray) for a in (x, y, state)):
+        raise ValueError("compare_stats: x, y and state must be DeviceArrays")
+    if zp is not None and np.ndim(zp):
+        raise ValueError("compare_stats: the zero point must be a scalar or None")
+    if x.dtype != np.float32:
+        raise ValueError(f"compare_stats: x must be float32 (got {x.dtype})")
+    if y.dtype == np.float32:
+        if scale is not None or zp is not None:
+            raise ValueError("compare_stats: scale and zero point belong to integer y only")
+    elif y.dtype in (np.int8, np.int16, np.int32, np.int64):
+        if scale is None:
+            raise ValueError("compare_stats: integer y needs its scale")
+    else:
+        raise ValueError(f"compare_stats: dtype {y.dtype} not supported (float32 or int8 / int16 / int32 / int64)")
+    if x.shape != y.shape:
+        raise ValueError(f"compare_stats: shapes differ ({x.shape} against {y.shape})")
+    if state.dtype != np.int64 or state.shape != (CMP_STATE,):
+        raise ValueError(f"compare_stats: state must be int64 [{CMP_STATE}] (got {state.dtype} {state.shape})")
+    if x.ptr % 4 or y.ptr % y.dtype.itemsize or state.ptr % 8:
+        raise ValueError("compare_stats: x and y need the alignment of their elements, state 8 bytes")
+    if x.size > CMP_MAX_N:
+        raise ValueError(f"compare_stats: more than {CMP_MAX_N} elements")
+    for arr, what in ((x, "x"), (y, "y"), (state, "state")):
+        if arr.ptr < arr.block.ptr or arr.ptr + arr.nbytes > arr.block.ptr + arr.block.size:
+            raise ValueError(f"compare_stats: {what} reaches outside its buffer")
+    if x.size == 0:
+        return
+    chunks = (x.size + CMP_CHUNK - 1) // CMP_CHUNK
+    scratch = DeviceArray((3 * chunks,), np.float64)
+    _lib.call("nqk_compare_stats", x.vp, y.vp, _lib.NQK_F32 if y.dtype == np.float32 else y.code,
+              float(np.float32(1.0 if scale is None else scale)), 0 if zp is None else int(zp),
+              0 if zp is None else 1, x.size, state.vp, scratch.vp, 3 * chunks)
+
+
 def where(cond: np.ndarray, a: DeviceArray, b: DeviceArray) -> DeviceArray:
     c = DeviceArray.from_host(np.asarray(cond).astype(np.int64))
     out_shape = tuple(np.broadcast_shapes(c.shape, a.shape, b.shape))

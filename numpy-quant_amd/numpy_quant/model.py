@@ -386,6 +386,61 @@ class Model:
 
         return self._rewrite(bit_width, params)
 
+    def compare(self, qmodel, batches, k=5, labels=None, values=True):
+        """What `qmodel` lost against this float model over an evaluation set: a
+        `compare.Report` with the error statistics of every value and the agreement of the two
+        models' top-k classes (compare.py defines the metrics).  Everything is accumulated on
+        the device (one kernel per value and batch); per batch only the two [B, k] index
+        arrays are downloaded, and the statistics once at the end.
+
+        `batches`: an iterable (a generator will do: one pass) of input lists as `__call__`
+        takes them.  `labels`: an iterable of integer arrays [B], one per batch, adds the
+        top-1 and top-k accuracy of both models.
+        `values=True` runs the float forward and the QModel's node loop, so that every value of
+        both models exists, and compares every value name the two share (constants once).  Both
+        models' values of one batch are alive at the same time, and the node loop is far
+        slower than the fused plan: size the evaluation batches accordingly.
+        `values=False` runs the QModel as `qmodel(inputs)` does, through the fused plan, and
+        compares the model outputs only: accuracy over a large evaluation set at full speed."""
+        from .compare import Agreement, Comparator, Report
+        if isinstance(self, QModel) or not isinstance(qmodel, QModel):
+            raise ValueError("compare: call it on the float Model with its QModel as the argument")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"compare: k must be a positive integer (got {k!r})")
+        if [v.name for v in self.outputs] != [v.name for v in qmodel.outputs]:
+            raise ValueError("compare: the two models have different outputs")
+        k = int(k)
+        cmp = Comparator()
+        agree = Agreement(labels is not None)
+        label_it = iter(labels) if labels is not None else None
+        eager = bool(values) or qmodel.keep_values
+        for inputs in batches:
+            lab = None
+            if label_it is not None:
+                try:
+                    lab = next(label_it)
+                except StopIteration:
+                    raise ValueError("compare: fewer label arrays than batches") from None
+            self._forward(inputs)
+            kept = {v.name: v.data for v in self.inputs if isinstance(v.data, FTensor)}
+            if not eager and qmodel._plan is None and qmodel.fuse:
+                qmodel.compile()
+            qmodel.set_inputs(inputs)
+            qmodel.run(eager=eager)
+            if values:
+                cmp.observe(self, qmodel, ref_inputs=kept)
+            else:
+                for ref, got in zip(self.outputs, qmodel.outputs):
+                    cmp.observe_pair(ref.name, ref.data, got.data, "variable",
+                                     ref.inputs[0].op if ref.inputs else "Input")
+            fidx, _ = _topk_output(self.outputs[0].data, k)
+            qidx, _ = _topk_output(qmodel.outputs[0].data, k)
+            agree.add(fidx.data, qidx.data, lab)
+        if agree.rows == 0:
+            raise ValueError("compare: no evaluation batch")
+        states = cmp.states()
+        return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
+
     def quantize_with(self, quant_params: dict, bit_width=8):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
