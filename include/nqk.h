@@ -455,7 +455,8 @@ int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64_t batch, i
                     int64_t lda, int64_t ldb, const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
                     const nqk_epilogue* params);
 /* Which kernel the last nqk_qgemm_fused call launched (tests / diagnostics): 0 small tiles
- * (k_qgemm_epi), 1 128x256 tiles (k_qgemm_big), 2 ping-pong 256x256 (k_qgemm_pp), 3 the
+ * (k_qgemm_epi), 1 128x256 tiles (k_qgemm_big), 2 retired and not reused (it was a ping-pong
+ * 256x256 kernel, measured no faster and removed), 3 the
  * persistent projection GEMM with the epilogue overlapped (k_proj), 4 the persistent 16x16x64
  * GEMM with two workgroups per CU (k_pg), 5 k_pg on 256 x 256 tiles (one 512-thread workgroup
  * per CU, B shared by its two row halves), 6 / 7 the same two with the GELU table epilogue

@@ -23,61 +23,23 @@
 #include "nqk_common.h"
 #include "nqk_numerics.h"
 
-#ifndef NQK_ATTN_DIAG
-#define NQK_ATTN_DIAG 0
-#endif
-#ifndef NQK_ATTN_EXPW
-#define NQK_ATTN_EXPW 4
-#endif
-#ifndef NQK_ATTN_PK
-#define NQK_ATTN_PK 1  // FAST path on element pairs with packed f32 arithmetic (0: scalar, for A/B)
-#endif
-#ifndef NQK_ATTN_PQ2
-#define NQK_ATTN_PQ2 1  // 1: P quantize without the clamp when no row can reach it, by fma rounding
-#endif
-#ifndef NQK_ATTN_EXP2
-#define NQK_ATTN_EXP2 1  // 1: rows whose arguments all lie in [-86.5, 0] take np_expf_safe2
-#endif
-#ifndef NQK_ATTN_PREL
-#define NQK_ATTN_PREL 1  // 1: P filter margin per element (|tf| 2^-21) instead of the row's (kpf 2^-20)
-#endif
-// P filter margins (NQK_ATTN_PREL), per element: the reference's t = RN(RN(e / tot) / s_p) is within
+namespace nqk {
+// scheduling window of the exp phase: independent exp chains between two sched_barriers
+constexpr int NQK_ATTN_EXPW = 4;
+// The FAST path works on element pairs with packed f32 arithmetic (the pairwise-sum accumulators
+// too: v_pk_add_f32); rows whose arguments all lie in [-86.5, 0] take np_expf_safe2; P is
+// quantized without the clamp when no row can reach it, by fma rounding.
+// P filter margins, per element (|tf| 2^-21 instead of the row's kpf 2^-20): the reference's
+// t = RN(RN(e / tot) / s_p) is within
 // (2u + u^2)|x| of x = e / (tot s_p) (u = 2^-24), kpf = RN(rtot rs_p) within (u + 3 2^-53)|x| / e.
 // Clamp-free path: r = rint(e kpf) exactly, so |t - e kpf| <= 3.0001 u |x| <= 4.5002 u |r| for |r| >= 1
 // (|x| <= |r| + 0.5 + ...; r = 0: 1.5 u, under the limit's 2 u): margin 4.75 u |r|.
 // Clamped path: tf = RN(e kpf) adds u, |t - tf| <= 4.0001 u |x| <= 4.002 u |tf|: margin 4.125 u |tf|.
 // Both then pass only below 0.5 - 2u, which also takes dd's and the measure's own roundings
 // (0.25 u each).  (Round 3 used 8 u for both: about twice the fallbacks.)
-#ifndef NQK_ATTN_PM_R
-#define NQK_ATTN_PM_R 0x1.3p-22f
-#endif
-#ifndef NQK_ATTN_PM_T
-#define NQK_ATTN_PM_T 0x1.08p-22f
-#endif
-#ifndef NQK_ATTN_PKL
-#define NQK_ATTN_PKL 0  // 1: clamped path tf = RN(e kpf + RN(e kpl)) (kpf + kpl = the double product):
-                        // |t - tf| <= 3.001 u |tf|, margin 3.125 u |tf| (A/B variant)
-#endif
-#ifndef NQK_ATTN_PSUM
-#define NQK_ATTN_PSUM 1  // 1: the pairwise-sum accumulators as packed pairs (v_pk_add_f32)
-#endif
-
-namespace nqk {
-#if (NQK_ATTN_DIAG & 128)
-// diagnostic builds: per launch, wave-tiles that took [0] the clamped exp (some argument below
-// -86.5), [1] the clamped P quantize, [2] the P exact fallback, [3] the context exact fallback
-__device__ unsigned long long g_attn_stats[4];
-extern "C" int nqk_attn_diag_stats(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_stats), 4 * sizeof(unsigned long long));
-  const unsigned long long z[4] = {0, 0, 0, 0};
-  if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stats), z, sizeof(z));
-  return 0;
-}
-#define NQK_ATTN_COUNT(i) \
-  do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_attn_stats[i], 1ull); } while (0)
-#else
-#define NQK_ATTN_COUNT(i) do { } while (0)
-#endif
+// The bit-exactness proof depends on these two numbers (tests/test_attn_filter_bound.py).
+constexpr float NQK_ATTN_PM_R = 0x1.3p-22f;
+constexpr float NQK_ATTN_PM_T = 0x1.08p-22f;
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -138,39 +100,13 @@ __device__ __forceinline__ float xor32f(float x) { return __int_as_float(xor32i(
 // 2^24, host-checked), the scores Div is a power of two (an exact f32 multiply), and the
 // P / context quantizations go through a rounding filter (t from one f32 product, exact
 // chain for any element within the product's error bound of a rounding boundary).
-#ifndef NQK_ATTN_WPE
-#define NQK_ATTN_WPE 0  // diagnostic builds: amdgpu_waves_per_eu(NQK_ATTN_WPE) occupancy target
-#endif
-#if NQK_ATTN_WPE
-#define NQK_ATTN_OCC __attribute__((amdgpu_waves_per_eu(NQK_ATTN_WPE, NQK_ATTN_WPE)))
-#else
-#define NQK_ATTN_OCC
-#endif
 // three workgroups (12 waves) per CU: the register budget is 168 per lane (the exp /
 // quantize phases are VALU-issue-bound, so the third wave per SIMD pays for a few spills)
-#ifndef NQK_ATTN_MINB
-#define NQK_ATTN_MINB 3
-#endif
-#ifndef NQK_ATTN_TAIL
-#define NQK_ATTN_TAIL 0  // 1: the last row tile of T = 193 .. 200 by the row-parallel path (round 5; measured no faster,
-                         // profiles/r05_attn_tail_dropped.txt: opt-in build)
-#endif
-constexpr int ATTN_TSTR = 232;
-// the row-parallel tail path applies: the shipped FAST configuration, T > 128 with at most 8 real
-// rows in the last tile and both pairwise-sum leaves of equal group counts (T = 193 .. 200)
-template <int NT, int TC, bool FAST>
-constexpr bool attn_tail() {
-  constexpr int TR = TC > 0 ? TC - 32 * (NT - 1) : 32;
-  constexpr int N2 = TC > 128 ? TC / 2 - (TC / 2) % 8 : 0;
-  return NQK_ATTN_TAIL && FAST && NQK_ATTN_PK && NQK_ATTN_EXP2 && NQK_ATTN_PQ2 && NQK_ATTN_PREL && !NQK_ATTN_PKL &&
-         NQK_ATTN_DIAG == 0 && TC > 128 && TR >= 1 && TR <= 8 && N2 / 8 == (TC - N2) / 8;
-}
-template <int NT, int TC, bool FAST>
-constexpr size_t attn_tail_lds() {
-  return attn_tail<NT, TC, FAST>() ? (size_t)(TC - 32 * (NT - 1)) * (ATTN_TSTR * 4 + NT * 32) : 0;
-}
+constexpr int NQK_ATTN_MINB = 3;
+// (the last row tile of T = 193 .. 200 by a row-parallel path, round 5: measured no faster,
+// profiles/r05_attn_tail_dropped.txt)
 template <int NT, int TC, bool FAST>  // TC: compile-time token count (0: runtime a.T)
-__global__ void __launch_bounds__(256, NQK_ATTN_MINB) NQK_ATTN_OCC
+__global__ void __launch_bounds__(256, NQK_ATTN_MINB)
 k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int8_t* __restrict__ Vg,
             int8_t* __restrict__ ctx, AttnArgs a) {
   constexpr int TP = NT * 32;  // padded tokens (score columns / PV contraction)
@@ -178,13 +114,6 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
   // group qq of score tile c (columns c*32 + 8qq .. + 7 of both halves) past the last
   // token: known at compile time when the token count is
   auto pad_group = [](int c, int qq) constexpr { return TC > 0 && c * 32 + 8 * qq >= TC; };
-  // NQK_ATTN_TAIL: the last row tile's TR real rows by the row-parallel path (below); its LDS: the
-  // rows' scores tS [TR][TSTR] f32 (rows 8 banks apart for ds_read_b32) and P bytes tP [TR][TP]
-  constexpr int TR = TC > 0 ? TC - 32 * (NT - 1) : 32;
-  constexpr int N2 = TC > 128 ? TC / 2 - (TC / 2) % 8 : 0, NG0 = N2 / 8, NG1 = (TC - N2) / 8, NG = NG0 + NG1;
-  constexpr int TL1 = TC - N2 - 8 * NG1;
-  constexpr bool TAILR = attn_tail<NT, TC, FAST>();
-  constexpr int TSTR = ATTN_TSTR;
   extern __shared__ __attribute__((aligned(16))) int8_t lds[];
   const int T = TC ? TC : a.T, PST = TC ? NT * 32 + 16 : a.PST;
   int8_t* Ks = lds;
@@ -192,8 +121,6 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
   auto vt_row = [&](int d) { return d * PST + (d >> 4) * 64; };  // byte offset of V^T row d
   int* colK = reinterpret_cast<int*>(Vt + 64 * PST + 256);  // rowsum(K[n]) * zq - zq*zk*64
   int* colV = colK + TP;                              // colsum(V[:, d]) * zp - zp*zv*T
-  float* const tS = reinterpret_cast<float*>(colV + 64);  // NQK_ATTN_TAIL scratch
-  int8_t* const tP = reinterpret_cast<int8_t*>(tS + (TAILR ? TR * TSTR : 0));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bh = blockIdx.x;
   const int img = bh / a.H, head = bh - img * a.H;
@@ -205,8 +132,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
   for (int idx = tid; idx < TP * 4; idx += 256) {
     const int row = idx >> 2, ch = idx & 3;
     const v4i z = {0, 0, 0, 0};
-    // (diagnostic 64: no K loads)
-    const v4i kv = (row < T && (NQK_ATTN_DIAG & 64) == 0) ? *reinterpret_cast<const v4i*>(k + row * 64 + ch * 16) : z;
+    const v4i kv = row < T ? *reinterpret_cast<const v4i*>(k + row * 64 + ch * 16) : z;
     *reinterpret_cast<v4i*>(Ks + swz64a(row, ch)) = kv;
   }
   // V^T by blocks of 4 tokens x 16 dims: four 16-B row loads, a 4 x 4 byte transpose per
@@ -218,14 +144,8 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int tok = 4 * rb + r;
-      // (diagnostic 64: no K / V loads; 4096: no V loads)
-      w[r] = (tok < T && (NQK_ATTN_DIAG & (64 | 4096)) == 0) ? *reinterpret_cast<const v4i*>(v + tok * 64 + c * 16)
-                                                               : v4i{0, 0, 0, 0};
+      w[r] = tok < T ? *reinterpret_cast<const v4i*>(v + tok * 64 + c * 16) : v4i{0, 0, 0, 0};
     }
-#if NQK_ATTN_DIAG & 1  // diagnostic builds only (wrong results): 1 = V^T staging skipped, 2 = exp
-                      // replaced by one add, 4 = P quantize replaced by a convert
-    if (blk == 0) Vt[0] = (int8_t)(w[0][0] ^ w[1][1] ^ w[2][2] ^ w[3][3]);
-#else
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       // out_k = [w0.byte k, w1.byte k, w2.byte k, w3.byte k] of dword column g
@@ -238,9 +158,8 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) *reinterpret_cast<uint32_t*>(Vt + vt_row(16 * c + 4 * g + kk) + 4 * rb) = o[kk];
     }
-#endif
   }
-  if constexpr ((NQK_ATTN_DIAG & 1024) == 0) __syncthreads();  // (diagnostic 1024: no workgroup barriers)
+  __syncthreads();
   for (int row = tid; row < TP; row += 256) {
     const v4i* kr = reinterpret_cast<const v4i*>(Ks + row * 64);
     colK[row] = (sum16a(kr[0]) + sum16a(kr[1]) + sum16a(kr[2]) + sum16a(kr[3])) * a.zq - a.kq;
@@ -253,7 +172,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
     s += __shfl_xor(s, 2, 64);
     if (part == 0) colV[d] = s * a.zp - a.kp;
   }
-  if constexpr ((NQK_ATTN_DIAG & 1024) == 0) __syncthreads();
+  __syncthreads();
 
   // pairwise-sum plan of a row (uniform): leaf l = [s0_l, s0_l + L_l), main part of
   // ng_l whole 8-groups from group g0_l, then a tail of tl_l < 8 columns
@@ -273,13 +192,8 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
         // (Q rows by LDS-DMA at the workgroup's start instead: no faster on the bench's data,
         // profiles/r04_attn_real_data.txt)
         const int qrow = min(m, T - 1);
-        if constexpr ((NQK_ATTN_DIAG & 2048) != 0) {  // (diagnostic 2048: Q rows from the LDS K image, no Q loads)
-          qb[0] = *reinterpret_cast<const v4i*>(Ks + swz64a(qrow, h));
-          qb[1] = *reinterpret_cast<const v4i*>(Ks + swz64a(qrow, 2 + h));
-        } else {
-          qb[0] = *reinterpret_cast<const v4i*>(q + qrow * 64 + h * 16);
-          qb[1] = *reinterpret_cast<const v4i*>(q + qrow * 64 + (2 + h) * 16);
-        }
+        qb[0] = *reinterpret_cast<const v4i*>(q + qrow * 64 + h * 16);
+        qb[1] = *reinterpret_cast<const v4i*>(q + qrow * 64 + (2 + h) * 16);
       }
       int rq = sum16a(qb[0]) + sum16a(qb[1]);
       rq += xor32i(rq);
@@ -307,10 +221,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
           const int vv = acc2[j][4 * qq + jj] - rowp - cv[jj];
           o[jj] = FAST ? (float)vv * a.s_pv : (float)((double)vv * (double)a.s_pv);
         }
-        if constexpr ((NQK_ATTN_DIAG & 16) != 0) {  // (diagnostic 16: context bytes without the quantize)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) qs[jj] = (int)o[jj];
-        } else if constexpr (FAST) {
+        if constexpr (FAST) {
           // rint(zp + t) for t = RN(o / s_ctx) approximated by tf = o rs (|t - tf| <= |tf| 2^-21),
           // on pairs: one v_pk_mul, clamp + magic-number rounding (round_magic2), and the
           // measure |tf| 2^-21 + |dd| of the four elements: below 0.5 - 2^-23 every element's
@@ -329,7 +240,6 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
                                                         __builtin_elementwise_max(__float_as_uint(m2), __float_as_uint(m3)));
           packed = pack4_low(s0, s1);
           if (__builtin_expect(__any(wm >= __float_as_uint(0x1.fffffcp-2f)), 0)) {
-            NQK_ATTN_COUNT(3);
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
               const int qv = quant_w(o[jj], a.s_ctx, a.rs_ctx, a.zp_ctx, a.lo, a.hi);
@@ -352,7 +262,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
   // a prefix of the query rows (a.QR < T): only the row tiles that hold one; a wave without a tile
   // has helped stage K / V and is done
   const int ntq = (a.QR + 31) >> 5;
-  for (int rt = wave; rt < (TAILR ? min(ntq, NT - 1) : ntq); rt += 4) {
+  for (int rt = wave; rt < ntq; rt += 4) {
     const int m0 = rt * 32, m = m0 + r32;
     v4i qb[2];
     const int nrowterm = q_rows(m, qb);
@@ -362,7 +272,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
     // max; only one tile's accumulators are live
     float e[NT][16];
     float mx = -__builtin_inff();
-    float mn = __builtin_inff();  // NQK_ATTN_EXP2: the smallest score of the whole groups
+    float mn = __builtin_inff();  // the smallest score of the whole groups (for esafe below)
     // whole groups: max / min of the integers (y = RN(v s_qkd) is monotone in v for s_qkd > 0,
     // host-checked on the FAST path), one v_max3_i32 / v_min3_i32 per pair; converted once
     int imx = INT32_MIN, imn = INT32_MAX;
@@ -383,7 +293,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
         for (int j = 0; j < 4; ++j) acc[4 * qq + j] = nrowterm - ck[j];
       }
 #pragma unroll
-      for (int s = 0; s < 2 && (NQK_ATTN_DIAG & 8) == 0; ++s) {  // (diagnostic 8: no score MFMAs)
+      for (int s = 0; s < 2; ++s) {
         const v4i ka = *reinterpret_cast<const v4i*>(Ks + swz64a(c * 32 + r32, 2 * s + h));
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ka, qb[s], acc, 0, 0, 0);
       }
@@ -394,9 +304,10 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
           for (int j = 0; j < 4; ++j) e[c][4 * qq + j] = 0.0f;
           continue;
         }
-        if constexpr (FAST && NQK_ATTN_PK) {
-          // pairs: one v_pk_mul for the dequantize + Div, a v_max3 for the row max; the
-          // -inf of padded columns only where the group straddles T (runtime lane half)
+        if constexpr (FAST) {
+          // pairs: one v_pk_mul for the dequantize + Div (RN(v s) / 2^k == RN(v (s / 2^k)) while
+          // both are normal, host-checked), a v_max3 for the row max; the -inf of padded columns
+          // only where the group straddles T (runtime lane half)
           const bool full = TC > 0 && c * 32 + 8 * qq + 8 <= TC;
 #pragma unroll
           for (int j = 0; j < 4; j += 2) {
@@ -407,7 +318,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
             e[c][r + 1] = y[1];
             if (full) {
               imx = max(imx, max(acc[r], acc[r + 1]));
-              if (NQK_ATTN_EXP2) imn = min(imn, min(acc[r], acc[r + 1]));
+              imn = min(imn, min(acc[r], acc[r + 1]));
             } else {
               mx = __builtin_fmaxf(mx, __builtin_fmaxf(y[0], y[1]));
             }
@@ -418,11 +329,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int r = 4 * qq + j, n = c * 32 + 8 * qq + 4 * h + j;
-          const int vv = acc[r];
-          float y;
-          // FAST: RN(v s) / 2^k == RN(v (s / 2^k)) while both are normal (host-checked)
-          if constexpr (FAST) y = (float)vv * a.s_qkd;
-          else y = div_rc_w((float)((double)vv * (double)a.s_qk), a.rdiv);
+          float y = div_rc_w((float)((double)acc[r] * (double)a.s_qk), a.rdiv);
           // -inf for padded columns: an add of a selected constant, so no branch
           y = y + (n < T ? 0.0f : -__builtin_inff());
           e[c][r] = y;
@@ -431,20 +338,19 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if constexpr (FAST && NQK_ATTN_PK) {
+    if constexpr (FAST) {
       if (imx != INT32_MIN) mx = __builtin_fmaxf(mx, (float)imx * a.s_qkd);
-      if (NQK_ATTN_EXP2 && imn != INT32_MAX) mn = (float)imn * a.s_qkd;
+      if (imn != INT32_MAX) mn = (float)imn * a.s_qkd;
     }
     {
       const float o = xor32f(mx);
       mx = o > mx ? o : mx;
     }
     const float nm = -mx;
-    // NQK_ATTN_EXP2: every argument y - max of the whole groups in [-86.5, 0] in all lanes
+    // every argument y - max of the whole groups in [-86.5, 0] in all lanes: np_expf_safe2
     // (RN(mn - mx) is the smallest; straddling groups keep np_expf_nonpos2 for their -inf pads)
-    const bool esafe = NQK_ATTN_EXP2 && __all(mn + nm >= NP_EXP_SAFE_LO);
-    if (!esafe) NQK_ATTN_COUNT(0);
-    if (FAST && NQK_ATTN_PK && NQK_ATTN_EXP2 && TC > 0 && (NQK_ATTN_DIAG & 2) == 0) {
+    const bool esafe = __all(mn + nm >= NP_EXP_SAFE_LO);
+    if constexpr (FAST && TC > 0) {
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
         if (esafe) {
@@ -468,7 +374,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
           }
         }
       }
-    } else if constexpr (FAST && NQK_ATTN_PK && (NQK_ATTN_DIAG & 2) == 0) {
+    } else if constexpr (FAST) {
 #pragma unroll
       for (int c = 0; c < NT; ++c)
 #pragma unroll
@@ -485,8 +391,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (pad_group(c, r >> 2)) continue;  // stays 0
-        if constexpr ((NQK_ATTN_DIAG & 2) != 0) e[c][r] = e[c][r] + nm;
-        else e[c][r] = np_expf_nonpos(e[c][r] + nm);  // y - max <= 0; -inf pads -> 0
+        e[c][r] = np_expf_nonpos(e[c][r] + nm);  // y - max <= 0; -inf pads -> 0
         // scheduling window of NQK_ATTN_EXPW independent exp chains
         if ((r % NQK_ATTN_EXPW) == NQK_ATTN_EXPW - 1) __builtin_amdgcn_sched_barrier(0);
       }
@@ -494,7 +399,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
     float ra[2][4], tv[2][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) ra[0][j] = ra[1][j] = tv[0][j] = tv[1][j] = 0.0f;
-    if constexpr (NQK_ATTN_PSUM && TC > 0) {
+    if constexpr (TC > 0) {
       // accumulators j, j + 1 as one packed pair: per lane the same IEEE adds in the same order
       v2f_t pa[2][2], pt[2][2];
 #pragma unroll
@@ -569,27 +474,18 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
     }
     const float tot = n2 ? leaf[0] + leaf[1] : leaf[0];
     const double rtot = 1.0 / (double)tot;
-    const double kpd = rtot * a.rs_p;
-    const float kpf = (float)kpd;  // t = e / tot / s_p within |t| 2^-22 of e * kpf
-    const float kpl = NQK_ATTN_PKL ? (float)(kpd - (double)kpf) : 0.0f;
-    constexpr float PM_T = NQK_ATTN_PKL ? 0x1.9p-23f : NQK_ATTN_PM_T;
-    // the filter's bound for the whole row (|tf| <= kpf (1 + 2^-23)), with margin
-    const float plim = 0.5f - 2.0f * __builtin_fmaf(kpf, 0x1p-21f, 0x1p-126f);
-    const float zp128 = a.zp_p_f + 128.0f, lo128 = a.lo_f + 128.0f, hi128 = a.hi_f + 128.0f;
+    const float kpf = (float)(rtot * a.rs_p);  // t = e / tot / s_p within |t| 2^-22 of e * kpf
     const float pqlo = a.lo_f - a.zp_p_f, pqhi = a.hi_f - a.zp_p_f, pmagic = 0x1.8p23f + a.zp_p_f;
     // ---- per score tile c: P = quantize(e / tot) (4 packed bytes per group, row sums),
     // then at once its share of O^T = V^T P^T (B operand = P row m, 16 consecutive tokens
     // per half), so only one tile's packed P is live
     rp = 0;
-    // NQK_ATTN_PQ2: when every lane's kpf <= pqhi (and pqlo <= 0), e kpf in [0, kpf] never
+    // when every lane's kpf <= pqhi (and pqlo <= 0), e kpf in [0, kpf] never
     // reaches a clamp (wave-uniform): s = RN(e kpf + pmagic) is rint(e kpf) + pmagic from
     // the exact product (one rounding fewer than tf = RN(e kpf), so still within |t| 2^-22 of
     // t), dd = RN(e kpf - (s - pmagic)) within 2^-25 of the exact distance (the limit takes
     // 2^-24 off for it)
-    // (diagnostic 512: the clamp-free path on every row, wrong results where a clamp is reached)
-    const bool pq_nc = NQK_ATTN_PQ2 && ((NQK_ATTN_DIAG & 512) != 0 || (pqlo <= 0.0f && __all(kpf <= pqhi)));
-    const float plim2 = plim - 0x1p-24f;
-    if (!pq_nc) NQK_ATTN_COUNT(1);
+    const bool pq_nc = pqlo <= 0.0f && __all(kpf <= pqhi);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -597,17 +493,14 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
       int dw[4];
-      if constexpr (FAST && (NQK_ATTN_DIAG & 4) == 0) {
+      if constexpr (FAST) {
         // t = e / tot / s_p is within thr of tf = e * kpf (|tf| <= kpf: e <= 1); where tf
-        // is farther than that from a rounding boundary, rint(tf) is rint(t).  Per
-        // element: the product, rint, the distance test, then v + 128 (v = the clamped
-        // integer, in [0, 255]) converted straight into its byte (v_cvt_pk_u8_f32) and
-        // the bytes flipped to two's complement at once (^ 0x80 each).
-        // the tile's largest distance |tf - r| (tf finite: e in [0, 1], kpf finite),
-        // one v_max per element; a tile with any element at or past plim recomputes the
-        // same tf per element and sends those elements through the exact chain
+        // is farther than that from a rounding boundary, rint(tf) is rint(t).
+        // worst: the tile's largest measure margin |r| + |tf - r| (tf finite: e in [0, 1], kpf
+        // finite), one v_max per element; a tile with any element at or past the limit recomputes
+        // the same tf per element and sends those elements through the exact chain
         float worst = 0.0f;
-        if (NQK_ATTN_PQ2 && NQK_ATTN_PK && pq_nc) {
+        if (pq_nc) {
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
             if (pad_group(c, qq)) {
@@ -619,18 +512,13 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
             const v2f_t s0 = __builtin_elementwise_fma(e0, k2, m2), s1 = __builtin_elementwise_fma(e1, k2, m2);
             const v2f_t dd0 = __builtin_elementwise_fma(e0, k2, -(s0 - m2));
             const v2f_t dd1 = __builtin_elementwise_fma(e1, k2, -(s1 - m2));
-            if constexpr (NQK_ATTN_PREL) {
-              // |t - e kpf| <= 3 2^-24 |x|: the margin NQK_ATTN_PM_R |r| (r = the rounded value; at
-              // r = 0 the limit itself covers it), the limit 0.5 - 2^-23 absorbs dd's own rounding
-              const v2f_t r0 = s0 - m2, r1 = s1 - m2;
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(r0[0]), NQK_ATTN_PM_R, __builtin_fabsf(dd0[0])),
-                                                             __builtin_fmaf(__builtin_fabsf(r0[1]), NQK_ATTN_PM_R, __builtin_fabsf(dd0[1]))));
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(r1[0]), NQK_ATTN_PM_R, __builtin_fabsf(dd1[0])),
-                                                             __builtin_fmaf(__builtin_fabsf(r1[1]), NQK_ATTN_PM_R, __builtin_fabsf(dd1[1]))));
-            } else {
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fabsf(dd0[0]), __builtin_fabsf(dd0[1])));
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fabsf(dd1[0]), __builtin_fabsf(dd1[1])));
-            }
+            // |t - e kpf| <= 3 2^-24 |x|: the margin NQK_ATTN_PM_R |r| (r = the rounded value; at
+            // r = 0 the limit itself covers it), the limit 0.5 - 2^-23 absorbs dd's own rounding
+            const v2f_t r0 = s0 - m2, r1 = s1 - m2;
+            worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(r0[0]), NQK_ATTN_PM_R, __builtin_fabsf(dd0[0])),
+                                                           __builtin_fmaf(__builtin_fabsf(r0[1]), NQK_ATTN_PM_R, __builtin_fabsf(dd0[1]))));
+            worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(r1[0]), NQK_ATTN_PM_R, __builtin_fabsf(dd1[0])),
+                                                           __builtin_fmaf(__builtin_fabsf(r1[1]), NQK_ATTN_PM_R, __builtin_fabsf(dd1[1]))));
             uint32_t w = pack4_low(s0, s1);
             if (!(TC > 0 && c * 32 + 8 * qq + 8 <= TC)) {  // padded columns: 0
               const int n = c * 32 + 8 * qq + 4 * h;
@@ -641,9 +529,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
             }
             dw[qq] = (int)w;
           }
-          // (diagnostic 256: the exact fallbacks skipped)
-          if ((NQK_ATTN_DIAG & 256) == 0 && __builtin_expect(__any(!(worst < (NQK_ATTN_PREL ? 0x1.fffff8p-2f : plim2))), 0)) {
-            NQK_ATTN_COUNT(2);
+          if (__builtin_expect(__any(!(worst < 0x1.fffff8p-2f)), 0)) {
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq) {
               if (pad_group(c, qq)) continue;
@@ -653,8 +539,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
                 const float x = e[c][4 * qq + j];
                 const float rr = __builtin_fmaf(x, kpf, pmagic) - pmagic;
                 const float d = __builtin_fmaf(x, kpf, -rr);
-                if (!(NQK_ATTN_PREL ? __builtin_fmaf(__builtin_fabsf(rr), NQK_ATTN_PM_R, __builtin_fabsf(d)) < 0x1.fffff8p-2f
-                                    : __builtin_fabsf(d) < plim2)) {
+                if (!(__builtin_fmaf(__builtin_fabsf(rr), NQK_ATTN_PM_R, __builtin_fabsf(d)) < 0x1.fffff8p-2f)) {
                   const int qv = n < T ? quant_w(div_rc_w(x, rtot), a.s_p, a.rs_p, a.zp_p, a.lo, a.hi) : 0;
                   dw[qq] = (int)(((uint32_t)dw[qq] & ~(0xffu << (8 * j))) | ((uint32_t)(qv & 0xff) << (8 * j)));
                 }
@@ -668,65 +553,44 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
             dw[qq] = 0;
             continue;
           }
-          if constexpr (NQK_ATTN_PK) {
-            // pairs: one v_pk_mul for tf, the clamp / magic-number rounding + byte pack of
-            // round_magic2 / pack4_low (nqk_numerics.h), |dd| into the tile's worst
-            v2f_t dd0, dd1;
-            const v2f_t ea = v2f_t{e[c][4 * qq], e[c][4 * qq + 1]}, eb = v2f_t{e[c][4 * qq + 2], e[c][4 * qq + 3]};
-            const v2f_t k2 = v2f_t{kpf, kpf}, kl2 = v2f_t{kpl, kpl};
-            const v2f_t tf0 = NQK_ATTN_PKL ? __builtin_elementwise_fma(ea, k2, ea * kl2) : ea * k2;
-            const v2f_t tf1 = NQK_ATTN_PKL ? __builtin_elementwise_fma(eb, k2, eb * kl2) : eb * k2;
-            const v2f_t s0 = round_magic2(tf0, pqlo, pqhi, pmagic, dd0);
-            const v2f_t s1 = round_magic2(tf1, pqlo, pqhi, pmagic, dd1);
-            if constexpr (NQK_ATTN_PREL) {
-              // |t - tf| <= 4 2^-24 |x|: the margin NQK_ATTN_PM_T |tf| per element (clamped elements:
-              // dd = 0, and the clamp decides them either way)
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(tf0[0]), PM_T, __builtin_fabsf(dd0[0])),
-                                                             __builtin_fmaf(__builtin_fabsf(tf0[1]), PM_T, __builtin_fabsf(dd0[1]))));
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(tf1[0]), PM_T, __builtin_fabsf(dd1[0])),
-                                                             __builtin_fmaf(__builtin_fabsf(tf1[1]), PM_T, __builtin_fabsf(dd1[1]))));
-            } else {
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fabsf(dd0[0]), __builtin_fabsf(dd0[1])));
-              worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fabsf(dd1[0]), __builtin_fabsf(dd1[1])));
-            }
-            uint32_t w = pack4_low(s0, s1);
-            if (!(TC > 0 && c * 32 + 8 * qq + 8 <= TC)) {  // padded columns: 0
-              const int n = c * 32 + 8 * qq + 4 * h;
-              uint32_t keep = 0;
+          // pairs: one v_pk_mul for tf, the clamp / magic-number rounding + byte pack of
+          // round_magic2 / pack4_low (nqk_numerics.h), |dd| into the tile's worst
+          // (tf = RN(e kpf + RN(e kpl)) with kpf + kpl the double product, margin 3.125 u |tf|:
+          // an A/B variant that was not kept)
+          v2f_t dd0, dd1;
+          const v2f_t ea = v2f_t{e[c][4 * qq], e[c][4 * qq + 1]}, eb = v2f_t{e[c][4 * qq + 2], e[c][4 * qq + 3]};
+          const v2f_t k2 = v2f_t{kpf, kpf};
+          const v2f_t tf0 = ea * k2;
+          const v2f_t tf1 = eb * k2;
+          const v2f_t s0 = round_magic2(tf0, pqlo, pqhi, pmagic, dd0);
+          const v2f_t s1 = round_magic2(tf1, pqlo, pqhi, pmagic, dd1);
+          // |t - tf| <= 4 2^-24 |x|: the margin NQK_ATTN_PM_T |tf| per element (clamped elements:
+          // dd = 0, and the clamp decides them either way)
+          worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(tf0[0]), NQK_ATTN_PM_T, __builtin_fabsf(dd0[0])),
+                                                         __builtin_fmaf(__builtin_fabsf(tf0[1]), NQK_ATTN_PM_T, __builtin_fabsf(dd0[1]))));
+          worst = __builtin_fmaxf(worst, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(tf1[0]), NQK_ATTN_PM_T, __builtin_fabsf(dd1[0])),
+                                                         __builtin_fmaf(__builtin_fabsf(tf1[1]), NQK_ATTN_PM_T, __builtin_fabsf(dd1[1]))));
+          uint32_t w = pack4_low(s0, s1);
+          if (!(TC > 0 && c * 32 + 8 * qq + 8 <= TC)) {  // padded columns: 0
+            const int n = c * 32 + 8 * qq + 4 * h;
+            uint32_t keep = 0;
 #pragma unroll
-              for (int j = 0; j < 4; ++j) keep |= (n + j < T ? 0xffu : 0u) << (8 * j);
-              w &= keep;
-            }
-            dw[qq] = (int)w;
-            continue;
+            for (int j = 0; j < 4; ++j) keep |= (n + j < T ? 0xffu : 0u) << (8 * j);
+            w &= keep;
           }
-          uint32_t packed = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int n = c * 32 + 8 * qq + 4 * h + j;
-            const float tf = e[c][4 * qq + j] * kpf;
-            const float r = __builtin_rintf(tf);
-            worst = __builtin_fmaxf(worst, __builtin_fabsf(tf - r));
-            float v = __builtin_amdgcn_fmed3f(r + zp128, lo128, hi128);
-            v = n < T ? v : 128.0f;  // padded columns: 0
-            packed = __builtin_amdgcn_cvt_pk_u8_f32(v, j, packed);
-          }
-          dw[qq] = (int)(packed ^ 0x80808080u);
+          dw[qq] = (int)w;
         }
-        const bool prel = NQK_ATTN_PREL && NQK_ATTN_PK;
-        if ((NQK_ATTN_DIAG & 256) == 0 && __builtin_expect(__any(!(worst < (prel ? 0x1.fffff8p-2f : plim))), 0)) {
-          NQK_ATTN_COUNT(2);
+        if (__builtin_expect(__any(!(worst < 0x1.fffff8p-2f)), 0)) {
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
             if (pad_group(c, qq)) continue;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const int n = c * 32 + 8 * qq + 4 * h + j;
-              const float ej = e[c][4 * qq + j];
-              const float tf = NQK_ATTN_PKL ? __builtin_fmaf(ej, kpf, ej * kpl) : ej * kpf;
-              const float cf = prel ? __builtin_amdgcn_fmed3f(tf, pqlo, pqhi) : tf;  // (the clamp as in the fast path)
+              const float tf = e[c][4 * qq + j] * kpf;
+              const float cf = __builtin_amdgcn_fmed3f(tf, pqlo, pqhi);  // (the clamp as in the fast path)
               const float dv = __builtin_fabsf(cf - __builtin_rintf(cf));
-              if (!(prel ? __builtin_fmaf(__builtin_fabsf(tf), PM_T, dv) < 0x1.fffff8p-2f : dv < plim)) {
+              if (!(__builtin_fmaf(__builtin_fabsf(tf), NQK_ATTN_PM_T, dv) < 0x1.fffff8p-2f)) {
                 const int qv = n < T ? quant_w(div_rc_w(e[c][4 * qq + j], rtot), a.s_p, a.rs_p, a.zp_p, a.lo, a.hi) : 0;
                 dw[qq] = (int)(((uint32_t)dw[qq] & ~(0xffu << (8 * j))) | ((uint32_t)(qv & 0xff) << (8 * j)));
               }
@@ -746,14 +610,9 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
         }
         uint32_t packed = 0;
         int qs[4];
-        if constexpr ((NQK_ATTN_DIAG & 4) != 0) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) qs[j] = (int)e[c][4 * qq + j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            qs[j] = quant_w(div_rc_w(e[c][4 * qq + j], rtot), a.s_p, a.rs_p, a.zp_p, a.lo, a.hi);
-        }
+        for (int j = 0; j < 4; ++j)
+          qs[j] = quant_w(div_rc_w(e[c][4 * qq + j], rtot), a.s_p, a.rs_p, a.zp_p, a.lo, a.hi);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int n = c * 32 + 8 * qq + 4 * h + j;
@@ -775,204 +634,11 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const v4i va = *reinterpret_cast<const v4i*>(Vt + vt_row(j * 32 + r32) + (2 * c + h) * 16);
-        if constexpr ((NQK_ATTN_DIAG & 32) != 0) acc2[j][c] ^= va[0] ^ pb[j];  // (diagnostic 32: no PV MFMAs)
-        else acc2[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(va, pb, acc2[j], 0, 0, 0);
+        acc2[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(va, pb, acc2[j], 0, 0, 0);
       }
     }
     rp += xor32i(rp);
     ctx_store(m, rp, acc2);
-  }
-  if constexpr (TAILR) {
-    if (wave == (NT - 1) % 4 && ntq == NT) {
-      const int rt = NT - 1, m = rt * 32 + r32;
-      v4i qb[2];
-      const int nrowterm = q_rows(m, qb);
-      int rp;
-      v16i acc2[2];
-      // ---- the last row tile (NQK_ATTN_TAIL): TR real query rows of 32.  The scores of those
-      // rows go to LDS, and the softmax / P quantize run with one lane per (row, NumPy
-      // accumulator n % 8) — NG + 1 elements a lane instead of 112 — then P comes back to the
-      // MFMA layout for P V.  Same operations per element as the full tile, the pairwise sum's
-      // accumulator chains and combination tree unchanged (every add of the tree is commutative).
-#pragma unroll
-      for (int c = 0; c < NT; ++c) {
-        v16i acc;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          if (pad_group(c, qq)) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[4 * qq + j] = 0;
-            continue;
-          }
-          const v4i ck = *reinterpret_cast<const v4i*>(colK + c * 32 + 8 * qq + 4 * h);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[4 * qq + j] = nrowterm - ck[j];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const v4i ka = *reinterpret_cast<const v4i*>(Ks + swz64a(c * 32 + r32, 2 * s + h));
-          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ka, qb[s], acc, 0, 0, 0);
-        }
-        if (r32 < TR) {
-#pragma unroll
-          for (int qq = 0; qq < 4; ++qq) {
-            if (pad_group(c, qq)) continue;
-            const v2f_t y01 = v2f_t{(float)acc[4 * qq], (float)acc[4 * qq + 1]} * v2f_t{a.s_qkd, a.s_qkd};
-            const v2f_t y23 = v2f_t{(float)acc[4 * qq + 2], (float)acc[4 * qq + 3]} * v2f_t{a.s_qkd, a.s_qkd};
-            *reinterpret_cast<float4*>(tS + r32 * TSTR + c * 32 + 8 * qq + 4 * h) = make_float4(y01[0], y01[1], y23[0], y23[1]);
-          }
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      // lane (ti, tj): row ti (rows >= TR mirror row TR - 1: computed, never stored), elements
-      // n = 8 g + tj (g < NG: NG0 groups of leaf 0, NG1 of leaf 1) and the tail element 8 NG + tj
-      const int ti = min(lane >> 3, TR - 1), tj = lane & 7, tb = lane & ~7;
-      const bool real = (lane >> 3) < TR;
-      float* const srow = tS + ti * TSTR;
-      // (streamed through LDS in three passes, so the path holds no per-element registers: the
-      // kernel's full tiles keep their register budget)
-      const float xt = tj < TL1 ? srow[8 * NG + tj] : -__builtin_inff();
-      float mxl = xt, mnl = tj < TL1 ? xt : __builtin_inff();
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const float v = srow[8 * g + tj];
-        mxl = __builtin_fmaxf(mxl, v), mnl = __builtin_fminf(mnl, v);
-      }
-#pragma unroll
-      for (int sh = 1; sh < 8; sh <<= 1) {
-        mxl = __builtin_fmaxf(mxl, __shfl_xor(mxl, sh, 64));
-        mnl = __builtin_fminf(mnl, __shfl_xor(mnl, sh, 64));
-      }
-      const float nm = -mxl;
-      const bool esafe = __all(mnl + nm >= NP_EXP_SAFE_LO);
-      // exp of elements g (leaf 0) and NG0 + g (leaf 1) as a pair, written back over the scores;
-      // NumPy's pairwise sum: accumulator tj of each leaf in increasing n (the pair's lanes), the
-      // 8 accumulators of a leaf combined ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) by xor
-      // butterflies, leaf 1's tail elements added in order, then leaf 0 + leaf 1
-      v2f_t ls;
-#pragma unroll
-      for (int g = 0; g < NG0; ++g) {
-        const v2f_t xa = v2f_t{srow[8 * g + tj], srow[8 * (NG0 + g) + tj]} + v2f_t{nm, nm};
-        const v2f_t ex = esafe ? np_expf_safe2(xa) : np_expf_nonpos2(xa);
-        ls = g == 0 ? ex : ls + ex;
-        if (real) srow[8 * g + tj] = ex[0], srow[8 * (NG0 + g) + tj] = ex[1];
-      }
-      const float et = np_expf_nonpos2(v2f_t{xt + nm, xt + nm})[0];  // (no tail element: -inf -> 0)
-#pragma unroll
-      for (int sh = 1; sh < 8; sh <<= 1) ls = ls + v2f_t{__shfl_xor(ls[0], sh, 64), __shfl_xor(ls[1], sh, 64)};
-      float leaf1 = ls[1];
-#pragma unroll
-      for (int t = 0; t < TL1; ++t) leaf1 = leaf1 + __shfl(et, tb + t, 64);
-      const float tot = ls[0] + leaf1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      const double rtot = 1.0 / (double)tot;
-      const float kpf = (float)(rtot * a.rs_p);
-      const float pqlo = a.lo_f - a.zp_p_f, pqhi = a.hi_f - a.zp_p_f, pmagic = 0x1.8p23f + a.zp_p_f;
-      const bool pq_nc = pqlo <= 0.0f && __all(kpf <= pqhi);
-      // P = quantize(e / tot) by the full tile's filtered fast path, exact chain where it cannot decide
-      const v2f_t k2 = v2f_t{kpf, kpf}, m2 = v2f_t{pmagic, pmagic};
-      constexpr int NPW = (NG + 4) / 4;
-      uint32_t pw[NPW];  // the lane's P bytes, 4 to a word: element g in byte g % 4 of word g / 4
-#pragma unroll
-      for (int w = 0; w < NPW; ++w) pw[w] = 0u;
-      auto put = [&](int g, int q) __attribute__((always_inline)) {
-        pw[g >> 2] = (pw[g >> 2] & ~(0xffu << (8 * (g & 3)))) | ((uint32_t)(q & 0xff) << (8 * (g & 3)));
-      };
-      auto get = [&](int g) __attribute__((always_inline)) { return (int)(int8_t)(pw[g >> 2] >> (8 * (g & 3))); };
-      uint32_t fails = 0;
-      auto quant_pair = [&](v2f_t e2, int& q0, int& q1, uint32_t& f0, uint32_t& f1) __attribute__((always_inline)) {
-        v2f_t s2, dd, mag;
-        if (pq_nc) {
-          s2 = __builtin_elementwise_fma(e2, k2, m2);
-          const v2f_t r2 = s2 - m2;
-          dd = __builtin_elementwise_fma(e2, k2, -r2);
-          mag = r2;
-        } else {
-          const v2f_t tf = e2 * k2;
-          s2 = round_magic2(tf, pqlo, pqhi, pmagic, dd);
-          mag = tf;
-        }
-        const float mr = pq_nc ? NQK_ATTN_PM_R : NQK_ATTN_PM_T;
-        f0 = !(__builtin_fmaf(__builtin_fabsf(mag[0]), mr, __builtin_fabsf(dd[0])) < 0x1.fffff8p-2f);
-        f1 = !(__builtin_fmaf(__builtin_fabsf(mag[1]), mr, __builtin_fabsf(dd[1])) < 0x1.fffff8p-2f);
-        q0 = (int)(int8_t)(__float_as_uint(s2[0]) & 0xffu);
-        q1 = (int)(int8_t)(__float_as_uint(s2[1]) & 0xffu);
-      };
-#pragma unroll
-      for (int g = 0; g < NG; g += 2) {
-        uint32_t f0, f1;
-        int q0, q1;
-        quant_pair(v2f_t{srow[8 * g + tj], srow[8 * (g + 1) + tj]}, q0, q1, f0, f1);
-        put(g, q0);
-        put(g + 1, q1);
-        fails |= (f0 << g) | (f1 << (g + 1));
-      }
-      {
-        uint32_t f0, f1;
-        int q0, qd;
-        quant_pair(v2f_t{et, et}, q0, qd, f0, f1);
-        put(NG, tj < TL1 ? q0 : 0);  // (no tail element: 0, so the byte sum below needs no mask)
-        fails |= (tj < TL1 ? f0 : 0u) << NG;
-      }
-      if (__builtin_expect(__any(fails != 0), 0)) {
-        NQK_ATTN_COUNT(2);
-#pragma unroll
-        for (int g = 0; g <= NG; ++g)
-          if ((fails >> g) & 1u) put(g, quant_w(div_rc_w(g < NG ? srow[8 * g + tj] : et, rtot), a.s_p, a.rs_p, a.zp_p, a.lo, a.hi));
-      }
-      int rps = 0;
-#pragma unroll
-      for (int w = 0; w < NPW; ++w) rps = __builtin_amdgcn_sdot4((int)pw[w], 0x01010101, rps, false);  // signed bytes
-#pragma unroll
-      for (int sh = 1; sh < 8; sh <<= 1) rps += __shfl_xor(rps, sh, 64);
-      if ((lane >> 3) < TR) {
-        int8_t* prow = tP + (lane >> 3) * TP;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) prow[8 * g + tj] = (int8_t)get(g);
-        if (tj < TL1) prow[8 * NG + tj] = (int8_t)get(NG);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      // ---- P back in the MFMA layout (rows >= TR and columns >= T: 0), then P V as the full tile
-      rp = __shfl(rps, min(r32, TR - 1) * 8, 64);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[j][r] = 0;
-#pragma unroll
-      for (int c = 0; c < NT; ++c) {
-        int dw[4];
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          if (pad_group(c, qq)) {
-            dw[qq] = 0;
-            continue;
-          }
-          const int n = c * 32 + 8 * qq + 4 * h;
-          uint32_t w = r32 < TR ? *reinterpret_cast<const uint32_t*>(tP + r32 * TP + n) : 0u;
-          if (!(c * 32 + 8 * qq + 8 <= TC)) {
-            uint32_t keep = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) keep |= (n + j < T ? 0xffu : 0u) << (8 * j);
-            w &= keep;
-          }
-          dw[qq] = (int)w;
-        }
-        const int xa = xor32i(h ? dw[0] : dw[2]);
-        const int xb = xor32i(h ? dw[1] : dw[3]);
-        v4i pb;
-        if (h) { pb[0] = xa; pb[1] = dw[2]; pb[2] = xb; pb[3] = dw[3]; }
-        else   { pb[0] = dw[0]; pb[1] = xa; pb[2] = dw[1]; pb[3] = xb; }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const v4i va = *reinterpret_cast<const v4i*>(Vt + vt_row(j * 32 + r32) + (2 * c + h) * 16);
-          acc2[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(va, pb, acc2[j], 0, 0, 0);
-        }
-      }
-      ctx_store(m, rp, acc2);
-    }
   }
 }
 
@@ -1000,12 +666,7 @@ k_attention(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const 
 // Every element goes through exactly k_attention<7, 197, true>'s operations (the same exps, sums,
 // P / context filters and exact fallbacks), so the context bytes are bit-identical to it
 // (tests/test_gpu_attention.py compares the two kernels).
-#ifndef NQK_ATTN16_QPF
-#define NQK_ATTN16_QPF 1
-#endif
-#ifndef NQK_ATTN16_MINB
-#define NQK_ATTN16_MINB 4  // workgroups (= waves per SIMD) per CU the register budget is sized for
-#endif
+constexpr int NQK_ATTN16_MINB = 4;  // workgroups (= waves per SIMD) per CU the register budget is sized for
 constexpr int A16_T = 197, A16_NT = 13, A16_KP = 208, A16_VT = 4 * 64 * 64;
 __host__ __device__ constexpr int a16_sw(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }  // = pg_sw
 __device__ __forceinline__ int a16_key(int c, int p) { return 16 * c + 8 * ((p >> 1) & 1) + 2 * (p >> 2) + (p & 1); }
@@ -1095,10 +756,10 @@ k_attn16(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int
   // a prefix of the query rows (a.QR < T): only the row tiles that hold one; a wave without a tile
   // has helped stage K / V and is done
   const int ntq = (a.QR + 15) >> 4;
-  v4i qnext = q_frag(wave);  // NQK_ATTN16_QPF: the next row tile's Q fragment loads under this one's work
+  v4i qnext = q_frag(wave);  // the next row tile's Q fragment loads under this one's work
   for (int rt = wave; rt < ntq; rt += NW) {
     const int m = rt * 16 + l15;  // the lane's query row
-    const v4i qb = NQK_ATTN16_QPF ? qnext : q_frag(rt);
+    const v4i qb = qnext;
     int nrowterm;
     {
       int rq = sum16a(qb);
@@ -1132,7 +793,7 @@ k_attn16(const int8_t* __restrict__ Qg, const int8_t* __restrict__ Kg, const int
         e[c][r + 1] = y[1];
       }
     }
-    if (NQK_ATTN16_QPF && rt + NW < ntq) qnext = q_frag(rt + NW);
+    if (rt + NW < ntq) qnext = q_frag(rt + NW);
     mx = __builtin_fmaxf(mx, (float)imx * a.s_qkd);
     mx = __builtin_fmaxf(mx, xor16f(mx));
     mx = __builtin_fmaxf(mx, xor32f(mx));
@@ -1374,7 +1035,6 @@ extern "C" int nqk_attention_fused(const int8_t* q, const int8_t* k, const int8_
                     !getenv("NQK_ATTN_EXACT");
   const size_t shm = (size_t)NT * 32 * 64 + (size_t)64 * a.PST + 256 + (size_t)(NT * 32 + 64) * 4;
   const dim3 grid((unsigned)batch_heads);
-  const size_t shm_tail = shm + attn_tail_lds<7, 197, true>();
   // round 6: the 16x16x64 four-lanes-per-row kernel for T = 197 FAST (NQK_ATTN16=0 keeps k_attention;
   // on the bench's data 154 -> 143 us, profiles/r06_attn16.txt)
   const char* a16v = getenv("NQK_ATTN16");
@@ -1392,7 +1052,7 @@ extern "C" int nqk_attention_fused(const int8_t* q, const int8_t* k, const int8_
   switch (T == 197 ? (fast ? -1 : 0) : NT) {
 #define A(n) case n: hipLaunchKernelGGL((k_attention<n, 0, false>), grid, dim3(256), shm, stream(), q, k, v, ctx, a); break;
     case -1:  // ViT at 224 px (196 patches + CLS): the pairwise plan and pads fold at compile time
-      hipLaunchKernelGGL((k_attention<7, 197, true>), grid, dim3(256), shm_tail, stream(), q, k, v, ctx, a);
+      hipLaunchKernelGGL((k_attention<7, 197, true>), grid, dim3(256), shm, stream(), q, k, v, ctx, a);
       break;
     case 0:
       hipLaunchKernelGGL((k_attention<7, 197, false>), grid, dim3(256), shm, stream(), q, k, v, ctx, a);

@@ -559,34 +559,16 @@ k_qgemm_epi(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
 // pieces of 16 rows x 64 B, lane-linear LDS image, the conflict-free chunk swizzle applied
 // to the SOURCE address) behind counted vmcnt waits and raw s_barriers.  A lane's 32
 // k-bytes of one MFMA pair are contiguous (k chunk 2*half + s): integer sums do not depend
-// on the k order, as long as A and B use the same one.  Both need K % 64 == 0 and
+// on the k order, as long as A and B use the same one.  It needs K % 64 == 0 and
 // precomputed weight column sums (zero-point COL term only).
 //   k_qgemm_big: 128x256 tiles, 4 waves, a 3-stage ring with one barrier per k-step, two
 //                blocks per CU (K % 192 == 0: the k loop is unrolled by the ring depth).
-//   k_qgemm_pp:  256x256 tiles, 8 waves in two groups of 4 that alternate roles every
-//                half k-step ("ping-pong"): while one group runs its 16 MFMAs on stage s,
-//                the other reads its stage-s fragments from LDS and issues its share of
-//                stage s+2, so each SIMD (one wave of each group) keeps its matrix pipe
-//                busy while the partner loads; a third fewer LDS-DMA bytes per MFMA.
+// (A 256x256 "ping-pong" form, two groups of 4 waves alternating MFMAs and loads every half
+// k-step, measured no faster and was removed: the k loop is bound by the LDS-DMA latency, not
+// the issue.)
 constexpr int GBN = 256, GBK = 64, GST = 3;
 constexpr int G_RP = 32;                          // epilogue rows per pass and wave
 constexpr int BIG_LDS = GST * (128 + GBN) * GBK;  // 72 KiB (>= 4 waves' staging, 36 KiB)
-#ifndef NQK_PP_PD
-#define NQK_PP_PD 2  // ping-pong ring: stages in flight ahead of the one being read
-#endif
-constexpr int PP_LDS = (NQK_PP_PD + 1) * (256 + GBN) * GBK;  // 96 KiB at depth 2 (>= 72 KiB staging)
-// Diagnostic builds only (tools/gemm_diag.sh, never the shipped library): bit 1 = no
-// global loads in the k loop, 2 = no LDS fragment reads, 4 = no k-step barrier, 8 = no MFMA
-// (k_qgemm_big).
-#ifndef NQK_DIAG
-#define NQK_DIAG 0
-#endif
-#ifndef NQK_BIG_RPRE
-#define NQK_BIG_RPRE 0  // 1: k_qgemm_big<RESID> issues pass 0's residual rows before the k loop (round 6 A/B: no gain)
-#endif
-#ifndef NQK_GLDS_FIRST
-#define NQK_GLDS_FIRST 0  // diagnostic builds: issue the next stage's LDS-DMA before the reads
-#endif
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(1))) void* gbl_ptr_t;
@@ -614,7 +596,7 @@ __device__ __forceinline__ float ln_dpp(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 // the residual rows of pass `pass` of a 128-row tile (rows mw + 32 pass + 4 it + (lane >> 4), the
-// lane's 4 columns gn0 ..): proj_epilogue's loads, also issued by k_qgemm_big before its k loop
+// lane's 4 columns gn0 ..): proj_epilogue's loads
 __device__ __forceinline__ void proj_res_load(const Epi& e, int mw, int gn0, bool cok, int M, int N, int lane, int pass,
                                               float4 (&dst)[G_RP / 4]) {
 #pragma unroll
@@ -623,10 +605,9 @@ __device__ __forceinline__ void proj_res_load(const Epi& e, int mw, int gn0, boo
     dst[it] = cok ? *reinterpret_cast<const float4*>(e.resid + (int64_t)gm * N + gn0) : make_float4(0, 0, 0, 0);
   }
 }
-// PRE0 (round 6): pass 0's residual rows were loaded by the caller before its k loop (rv0)
-template <int EPI, bool I32, bool F32X, int ASH = 0, bool LN = false, bool PRE0 = false>
+template <int EPI, bool I32, bool F32X, int ASH = 0, bool LN = false>
 __device__ __forceinline__ void proj_epilogue(int8_t* lds, v16i (&acc)[4][2], const Epi& e, int mw, int ncol0,
-                                              int M, int N, int wave, int lane, const float4 (*rv0)[G_RP / 4] = nullptr) {
+                                              int M, int N, int wave, int lane) {
   constexpr int RP = G_RP;
   static_assert(!LN || EPI == EPI_RESID, "proj_epilogue: the LayerNorm fuses into the residual epilogue");
   const int r32 = lane & 31, half = lane >> 5;
@@ -653,14 +634,7 @@ __device__ __forceinline__ void proj_epilogue(int8_t* lds, v16i (&acc)[4][2], co
   // accumulators of earlier passes are dead by then)
   float4 rv[2][RP / 4];
   auto load_res = [&](int pass, float4 (&dst)[RP / 4]) { proj_res_load(e, mw, gn0, cok, M, N, lane, pass, dst); };
-  if constexpr (EPI == EPI_RESID) {
-    if constexpr (PRE0) {
-#pragma unroll
-      for (int it = 0; it < RP / 4; ++it) rv[0][it] = (*rv0)[it];
-    } else {
-      load_res(0, rv[0]);
-    }
-  }
+  if constexpr (EPI == EPI_RESID) load_res(0, rv[0]);
 #pragma unroll
   for (int pass = 0; pass < 128 / RP; ++pass) {
 #pragma unroll
@@ -806,31 +780,17 @@ __device__ __forceinline__ void proj_epilogue(int8_t* lds, v16i (&acc)[4][2], co
 
 // XCD-aware tile order: XCD x (= blockIdx % XCDs) walks one contiguous band of tiles, so
 // the blocks that share an A row panel share one L2
-#ifndef NQK_STAGGER
-#define NQK_STAGGER 0
-#endif
-#ifndef NQK_LN_DIAG
-#define NQK_LN_DIAG 0
-#endif
-#ifndef NQK_TILE_ORDER
-#define NQK_TILE_ORDER 0  // diagnostic builds: 1 = plain block order, 2 = column-panel bands
-#endif
 __device__ __forceinline__ int xcd_tile(int nwg, int xc) {
   int wg = blockIdx.x;
-  if (NQK_TILE_ORDER != 1 && nwg >= xc && xc > 0) {
+  if (nwg >= xc && xc > 0) {
     wg = xcd_remap<int>(wg, nwg, xc);
   }
   return wg;
 }
 // tile (tm, tn) of tile id wg: row-panel-major (blocks with consecutive ids share A rows)
 __device__ __forceinline__ void tile_of(int wg, int tiles_m, int tiles_n, int& tm, int& tn) {
-  if (NQK_TILE_ORDER == 2) {
-    tn = wg / tiles_m;
-    tm = wg - tn * tiles_m;
-  } else {
-    tm = wg / tiles_n;
-    tn = wg - tm * tiles_n;
-  }
+  tm = wg / tiles_n;
+  tn = wg - tm * tiles_n;
 }
 
 // B4: the weights are int4 (|w| <= 8), nibble-packed by nqk_pack_b4: a B row of one
@@ -850,11 +810,6 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
   constexpr int PW = AP + BP;                  // LDS-DMA ops per wave per stage (6 / 4)
   constexpr int STAGE = GBM * GBK + GBN * BROW;  // 24 / 16 KiB
   extern __shared__ __attribute__((aligned(16))) int8_t lds[];
-#if NQK_STAGGER
-  // diagnostic: the second block of each CU in the first dispatch round starts late
-  if (blockIdx.x >= 256 && blockIdx.x < 512)
-    for (int i = 0; i < NQK_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
   int tm, tn;
   tile_of(xcd_tile(tiles_m * tiles_n, e.xcds), tiles_m, tiles_n, tm, tn);
   const int m0 = tm * GBM, n0 = tn * GBN;
@@ -883,7 +838,6 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
   }
   auto issue = [&](int st, auto SLOT) {
     constexpr int sl = decltype(SLOT)::value;
-    if constexpr ((NQK_DIAG & 1) != 0) return;
     int8_t* slot = lds + sl * STAGE;
     const int k0 = st * GBK;
     const int64_t kb = st * bstep;
@@ -913,21 +867,13 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
     } else {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW) : "memory");  // stage kt+1 may fly
     }
-    if constexpr ((NQK_DIAG & 4) == 0) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     const int8_t* sa = lds + sl * STAGE;
     const int8_t* sb = sa + GBM * GBK;
-    if constexpr (NQK_GLDS_FIRST && decltype(refill)::value) issue(kt + 2, std::integral_constant<int, (sl + 2) % GST>{});
     v4i fa[2][4], fb[2][2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      if constexpr ((NQK_DIAG & 2) != 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[s][i] = v4i{kt + i, lane, s, 1};
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fb[s][j] = v4i{kt + j, lane, s, 2};
-        continue;
-      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) fa[s][i] = *reinterpret_cast<const v4i*>(sa + swz64(i * 32 + r32, 2 * half + s));
 #pragma unroll
@@ -943,31 +889,15 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
         }
       }
     }
-    if constexpr (!NQK_GLDS_FIRST && decltype(refill)::value) issue(kt + 2, std::integral_constant<int, (sl + 2) % GST>{});
+    if constexpr (decltype(refill)::value) issue(kt + 2, std::integral_constant<int, (sl + 2) % GST>{});
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr ((NQK_DIAG & 8) == 0)
-            acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
-          else
-            acc[i][j][0] ^= fa[s][i][0] ^ fb[s][j][1];
-        }
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
     // issue order: the s=0 fragment reads, then the MFMAs with the s=1 reads and the
     // next stage's loads spread between them
-#if NQK_GLDS_FIRST
-    if constexpr (decltype(refill)::value) __builtin_amdgcn_sched_group_barrier(0x020, PW, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-    for (int g = 0; g < 6; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 10, 0);
-    return;
-#endif
     __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
     for (int g = 0; g < 6; ++g) {
@@ -990,16 +920,8 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
   using S1 = std::integral_constant<int, 1>;
   using S2 = std::integral_constant<int, 2>;
   const int nk = K / GBK;  // a multiple of 3 (host-checked): the ring slot of step kt is kt % 3
-  // RESID (NQK_BIG_RPRE=1, opt-in; round 6, no gain: profiles/r06_big_rpre_dropped.txt): pass 0's residual rows issued before the k loop, so
-  // the epilogue does not open on their HBM latency (ViT-Ti's residual GEMMs: 2 workgroups per CU
-  // at most, latency-bound); the vmcnt waits of the loop count LDS-DMA operations only, so these
-  // older loads are waited for with the first stage (vmcnt is in order)
-  constexpr bool RPRE = EPI == EPI_RESID && NQK_BIG_RPRE;
-  float4 rv0[G_RP / 4];
-  if constexpr (RPRE) {
-    const int gn0 = n0 + wn * 64 + (lane & 15) * 4;
-    proj_res_load(e, m0, gn0, gn0 < N, M, N, lane, 0, rv0);
-  }
+  // (RESID with pass 0's residual rows issued before the k loop: round 6, no gain,
+  // profiles/r06_big_rpre_dropped.txt)
   issue(0, S0{});
   issue(1, S1{});
   for (int kt = 0; kt + 3 < nk; kt += 3) {  // every step refills (stage kt + 4 < nk)
@@ -1012,124 +934,7 @@ k_qgemm_big(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
   kstep(nk - 1, S2{}, F_{}, T_{});
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  if constexpr (RPRE) proj_epilogue<EPI, I32, F32X, B4 ? 4 : 0, LN, true>(lds, acc, e, m0, n0 + wn * 64, M, N, wave, lane, &rv0);
-  else proj_epilogue<EPI, I32, F32X, B4 ? 4 : 0, LN>(lds, acc, e, m0, n0 + wn * 64, M, N, wave, lane);
-}
-
-template <int EPI, bool I32, bool F32X>
-__global__ void __launch_bounds__(512, 1)
-k_qgemm_pp(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, int N, int K, int lda, int ldb,
-           int tiles_m, int tiles_n, Epi e) {
-  constexpr int BM = 256;
-  constexpr int STAGE = (BM + GBN) * GBK;  // 32 KiB
-  extern __shared__ __attribute__((aligned(16))) int8_t lds[];
-  int tm, tn;
-  tile_of(xcd_tile(tiles_m * tiles_n, e.xcds), tiles_m, tiles_n, tm, tn);
-  const int m0 = tm * BM, n0 = tn * GBN;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar branches
-  const int grp = wave >> 2, wn = wave & 3;
-  const int r32 = lane & 31, half = lane >> 5;
-
-  // LDS-DMA: each wave moves 2 A and 2 B pieces (16 rows x 64 B) of every stage
-  const int prow = lane >> 2, ppos = lane & 3;
-  const int8_t* asrc[2];
-  const int8_t* bsrc[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int row = (wave * 2 + p) * 16 + prow;  // 0..255
-    const int sw = (ppos ^ ((row >> 2) & 3)) * 16;
-    asrc[p] = A + (int64_t)min(m0 + row, M - 1) * lda + sw;
-    bsrc[p] = Bt + (int64_t)min(n0 + row, N - 1) * ldb + sw;
-  }
-  auto issue = [&](int st, int slot) {
-    int8_t* sl = lds + slot * STAGE;
-    const int k0 = st * GBK;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(asrc[p] + k0), (lds_ptr_t)(sl + (wave * 2 + p) * 1024), 16, 0, 0);
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[p] + k0),
-                                       (lds_ptr_t)(sl + BM * GBK + (wave * 2 + p) * 1024), 16, 0, 0);
-  };
-
-  v16i acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-  v4i fa[2][4], fb[2][2];
-  const int nk = K / GBK;
-  // load segment: this wave's fragments of stage st from its slot, then its share of
-  // stage st+2 into slot (st+2) % 3 (last read two half-steps ago); lgkmcnt(0) before the
-  // barrier that ends the segment (fragments in registers, slot reads retired)
-  auto load_seg = [&](int st, int slot) {
-    const int8_t* sa = lds + slot * STAGE;
-    const int8_t* sb = sa + BM * GBK;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        fa[s][i] = *reinterpret_cast<const v4i*>(sa + swz64(grp * 128 + i * 32 + r32, 2 * half + s));
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        fb[s][j] = *reinterpret_cast<const v4i*>(sb + swz64(wn * 64 + j * 32 + r32, 2 * half + s));
-    }
-    if (st + NQK_PP_PD < nk) issue(st + NQK_PP_PD, slot == 0 ? NQK_PP_PD : slot - 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  // compute segment: 16 MFMAs on the fragments of the last load segment; s_setprio keeps
-  // the cluster between its barriers and ahead of the partner's loads on the SIMD
-  auto compute_seg = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto barrier = [&]() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-  };
-  // stage st+1 complete for this wave: after each segment, the wave's own pieces of the
-  // stage after the one it reads next have landed (at most stage st+2's 4 in flight)
-  auto wait_next = [&](int st) {  // allow this wave's pieces of stages st+2 .. st+PD
-    const int n = min(st + NQK_PP_PD, nk - 1) - (st + 1);
-    if (n >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (n == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-  issue(0, 0);
-  for (int st = 1; st < NQK_PP_PD && st < nk; ++st) issue(st, st);
-  wait_next(-1);
-  barrier();
-  // the stagger: group 1 runs one half-step behind group 0, so in every barrier interval
-  // one group loads while the other computes; both run the same segment sequence
-  if (grp == 1) barrier();
-  int slot = 0;
-  for (int st = 0; st < nk; ++st) {
-    load_seg(st, slot);
-    wait_next(st);
-    barrier();
-    compute_seg();
-    wait_next(st);
-    barrier();
-    slot = slot == NQK_PP_PD ? 0 : slot + 1;
-  }
-  if (grp == 0) barrier();  // same barrier count for both groups
-  // every load segment ended (lgkmcnt(0)) before the last barrier: the ring is free
-  proj_epilogue<EPI, I32, F32X>(lds, acc, e, m0 + grp * 128, n0 + wn * 64, M, N, wave, lane);
+  proj_epilogue<EPI, I32, F32X, B4 ? 4 : 0, LN>(lds, acc, e, m0, n0 + wn * 64, M, N, wave, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1210,12 +1015,6 @@ __device__ __forceinline__ void buf_lds16(rsrc_t r, void* l, uint32_t voff, uint
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)l, 16, voff, soff, 0, 0);
 }
 
-#ifndef NQK_PJ_DIAG
-#define NQK_PJ_DIAG 0  // diagnostic builds only: 1 = no epilogue stores, 2 = trivial epilogue math,
-                      // 4 = no operand loads, 8 = no k-loop barriers, 16 = no fragment reads,
-                      // 32 = no epilogue (results garbage)
-#endif
-
 // QKV / GELU epilogue of NG register groups of a transposed tile: group x = accumulators
 // a[x][0..3] = 4 consecutive columns (column terms ct[x], biases bs[x]) of this lane's
 // row; per element the operations of epi_row4 with the F32X rounding filters.  The fast
@@ -1253,10 +1052,6 @@ __device__ __forceinline__ void p2_quant(const Epi& e, const int (&a)[NG][4], co
     const int v = (a[x >> 2][x & 3] >> ASH) - ct[x >> 2][x & 3];
     const float h = __int_as_float(bs[x >> 2][x & 3]) + (float)v * sacc;  // the f64 dequantize, exactly (F32X)
     hv[x] = h;
-    if constexpr ((NQK_PJ_DIAG & 2) != 0) {
-      packed[x >> 2] = __builtin_amdgcn_cvt_pk_u8_f32((float)(v & 255), x & 3, packed[x >> 2]);
-      continue;
-    }
     float r;
     const float d = measure(h, r);
     worst = __builtin_elementwise_max(worst, __float_as_uint(d));
@@ -1342,7 +1137,6 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
   };
   auto issue_stage = [&](const Src& s, auto KT, int slot) __attribute__((always_inline)) {
     constexpr int kt = decltype(KT)::value;
-    if constexpr ((NQK_PJ_DIAG & 4) != 0) return;  // diagnostic: no operand loads
     int8_t* st = lds + slot * STG;
     // rows row0 and row0 + 16 (same swizzle: (row >> 2) & 3 repeats every 16 rows)
     buf_lds16(r_a, st + (2 * wave) * 1024, va, s.sa + kt * GBK);
@@ -1386,7 +1180,6 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
   auto read_frag = [&](int slot, int s, int q, v4i (&fa)[4], v4i (&fb)[2]) __attribute__((always_inline)) {
     const int8_t* sa = lds + slot * STG;
     const int8_t* sb = sa + 256 * GBK;
-    if constexpr ((NQK_PJ_DIAG & 16) != 0) return;  // diagnostic: no fragment reads
     if (q < 4) {
       fa[q] = *reinterpret_cast<const v4i*>(sa + swz64(wm * 128 + q * 32 + r32, 2 * half + s));
     } else {
@@ -1432,13 +1225,6 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
   // ---- the epilogue of tile s (accumulators in acc)
   auto epilogue = [&](const Src& s) __attribute__((always_inline)) {
     const int r0 = s.r0, n0 = s.tn * GBN;
-    if constexpr ((NQK_PJ_DIAG & 32) != 0) {  // diagnostic: no epilogue
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[i][j][0]));
-      return;
-    }
     if constexpr (RESID) {
       int ct[2];
       float bias[2];
@@ -1544,11 +1330,7 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
           // 16..31 of the tile: one 16-byte store per lane instead of four 4-byte ones
           const uint32_t x0 = pswap32(half ? pk[0] : pk[2]), x1 = pswap32(half ? pk[1] : pk[3]);
           const v4u st = half ? v4u{x0, pk[2], x1, pk[3]} : v4u{pk[0], x0, pk[1], x1};
-          if constexpr ((NQK_PJ_DIAG & 1) != 0) {
-            asm volatile("" ::"v"(st[0] ^ st[1] ^ st[2] ^ st[3]));
-          } else {
-            __builtin_amdgcn_raw_buffer_store_b128(st, out, rowoff[i] + j * 32, 0, 0);
-          }
+          __builtin_amdgcn_raw_buffer_store_b128(st, out, rowoff[i] + j * 32, 0, 0);
         }
       });
     }
@@ -1605,7 +1387,7 @@ k_proj(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N
         else
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(younger) : "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr ((NQK_PJ_DIAG & 8) == 0) __builtin_amdgcn_s_barrier();  // diagnostic: none
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       } else if constexpr (B4) {
         lgkm_wait();
@@ -1711,9 +1493,7 @@ k_ln_quant(const float* __restrict__ x, const float* __restrict__ g, const float
 // ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) combine and the leaf tree are xor-butterflies
 // (float addition is commutative, only the grouping matters).  2*NL lanes per row,
 // 64 / (2*NL) rows per wave; every load and store is 16 / 4 bytes per lane.
-#ifndef NQK_LN_LB
-#define NQK_LN_LB 1
-#endif
+constexpr int NQK_LN_LB = 1;
 template <int NL, bool MQ = false>
 __global__ void __launch_bounds__(256, NQK_LN_LB)
 k_ln_quant_reg(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
@@ -1727,15 +1507,8 @@ k_ln_quant_reg(const float* __restrict__ x, const float* __restrict__ g, const f
   const int c0 = leaf * LF + 4 * grp;
   const float* xr = x + (ok ? row : 0) * COLS + c0;
   float4 xv[NI];
-#if NQK_LN_DIAG
-  // diagnostic only (wrong values): fully coalesced loads of the wave's rows
-  const float* wbase = x + (((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63)) / LPR) * COLS;
-#pragma unroll
-  for (int i = 0; i < NI; ++i) xv[i] = *reinterpret_cast<const float4*>(wbase + (i * 64 + lane) * 4);
-#else
 #pragma unroll
   for (int i = 0; i < NI; ++i) xv[i] = *reinterpret_cast<const float4*>(xr + 8 * i);
-#endif
   float a0 = xv[0].x, a1 = xv[0].y, a2 = xv[0].z, a3 = xv[0].w;
 #pragma unroll
   for (int i = 1; i < NI; ++i) {
@@ -1788,25 +1561,17 @@ k_ln_quant_reg(const float* __restrict__ x, const float* __restrict__ g, const f
 // The same register tree, with the rows moved through LDS so that every global load and
 // store of a wave is one contiguous 1 KiB (the tree's lane layout reads 16 B at a 32-B
 // stride: 8 segments per row and instruction).  A wave's RW = 64 / (2 NL) rows are
-// contiguous in memory: loaded linearly into the wave's own LDS image (16 B of pad per
-// 96-column leaf: conflict-free reads in the tree layout), read in the tree layout,
-// and the packed int8 results written back into LDS (784-B rows: conflict-free dword
-// writes) and stored linearly.  No workgroup barrier: each wave owns its LDS image.
+// contiguous in memory: loaded linearly by LDS-DMA (buffer_load ... lds, round 5) into the
+// wave's own XOR-swizzled LDS image (ln_swz below), read in the tree layout, and the packed
+// int8 results written back into LDS (784-B rows: conflict-free dword writes) and stored
+// linearly.  No workgroup barrier: each wave owns its LDS image.  The f32 element arithmetic
+// runs on packed pairs (round 5).
 // (Measured slower and dropped in round 4: an f32 rounding filter in front of the f64
 // quantize chain, 40.9 vs 39.3 us per launch at 50432 x 768, profiles/r04_ln_filter_dropped.txt;
 // two row groups per wave with the second group's loads under the first's work, 40.8 vs
 // 39.7 us, profiles/r04_ln_gpw_dropped.txt.)
-#ifndef NQK_LN_PK
-#define NQK_LN_PK 1  // 1: the f32 element arithmetic of the LDS variant as packed pairs (round 5)
-#endif
-#ifndef NQK_LN_NT
-#define NQK_LN_NT 0  // 1: the f32 row loads non-temporal (read once; A/B variant, round 5)
-#endif
-#ifndef NQK_LN_DMA
-#define NQK_LN_DMA 1  // 1: the rows by LDS-DMA (buffer_load ... lds) into an XOR-swizzled image (round 5)
-#endif
-// NQK_LN_DMA: LDS-DMA writes a wave's 64 x 16 B contiguously, so the image cannot carry the
-// per-leaf pad; instead 16-B chunk c of row r sits at position c ^ 2 h (bits 1-2 flipped, inside
+// LDS-DMA writes a wave's 64 x 16 B contiguously, so the image cannot carry a
+// per-leaf pad against bank conflicts; instead 16-B chunk c of row r sits at position c ^ 2 h (bits 1-2 flipped, inside
 // the leaf's aligned 8-chunk blocks: an involution), h = (leaf >> 1) & 3 for 8 leaves, r & 3 for
 // 4 and 2.  A tree read (chunk 24 leaf + 2 i + grp of each lane's row) then puts the 16 lanes of
 // every ds_read_b128 lane group on 16 different 4-bank slots (rows of 24 NL chunks = 0 mod 16;
@@ -1821,8 +1586,7 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
                double hi, LnQ mq) {
   constexpr int LF = 96, LPR = NL * 2, NI = LF / 8, COLS = NL * LF, RW = 64 / LPR;
   constexpr int CH = COLS / 4;                      // 16-B chunks per row
-  constexpr bool DMA = NQK_LN_DMA;
-  constexpr int RSI = COLS * 4 + (DMA ? 0 : NL * 16);  // LDS bytes per input row
+  constexpr int RSI = COLS * 4;                     // LDS bytes per input row
   constexpr int RSO = COLS + 16;                    // LDS bytes per output row
   constexpr int WLDS = RW * RSI;                    // >= RW * RSO
   constexpr int NLD = RW * CH / 64, NST = RW * COLS / 16 / 64;
@@ -1833,36 +1597,15 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
   const int64_t row0 = ((int64_t)blockIdx.x * WPB + wave) * RW;
   if (row0 >= rows) return;  // (uniform per wave; no workgroup barrier follows)
   // ---- linear loads (rows past the end read the last row; not stored)
-  if constexpr (DMA) {
-    // position P = 64 k + lane of the image <- row P / CH, chunk ln_swz(P % CH)
-    const rsrc_t rx = make_rsrc(x, (uint32_t)((uint64_t)rows * COLS * 4));
+  // position P = 64 k + lane of the image <- row P / CH, chunk ln_swz(P % CH)
+  const rsrc_t rx = make_rsrc(x, (uint32_t)((uint64_t)rows * COLS * 4));
 #pragma unroll
-    for (int k = 0; k < NLD; ++k) {
-      const int P = k * 64 + lane, r = P / CH, c = ln_swz(NL, r, P - r * CH);
-      const int64_t gr = row0 + r < rows ? row0 + r : rows - 1;
-      buf_lds16(rx, wl + k * 1024, (uint32_t)(gr * COLS + c * 4) * 4u, 0u);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  float4 ld[NLD];
-#pragma unroll
-  for (int k = 0; k < NLD && !DMA; ++k) {
-    const int C = k * 64 + lane, r = C / CH, c = C - r * CH;
+  for (int k = 0; k < NLD; ++k) {
+    const int P = k * 64 + lane, r = P / CH, c = ln_swz(NL, r, P - r * CH);
     const int64_t gr = row0 + r < rows ? row0 + r : rows - 1;
-    if constexpr (NQK_LN_NT) {
-      typedef float v4f_nt __attribute__((ext_vector_type(4)));
-      const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt*>(x + gr * COLS + c * 4));
-      ld[k] = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      ld[k] = *reinterpret_cast<const float4*>(x + gr * COLS + c * 4);
-    }
+    buf_lds16(rx, wl + k * 1024, (uint32_t)(gr * COLS + c * 4) * 4u, 0u);
   }
-#pragma unroll
-  for (int k = 0; k < NLD && !DMA; ++k) {
-    const int C = k * 64 + lane, r = C / CH, c = C - r * CH;
-    *reinterpret_cast<float4*>(wl + r * RSI + c * 16 + (c / (LF / 4)) * 16) = ld[k];
-  }
-  if constexpr (!DMA) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   // ---- the tree layout: lane (row r, leaf, grp) holds columns leaf*96 + 8i + 4grp + 0..3
   const int r = lane / LPR, u = lane % LPR, leaf = u >> 1, grp = u & 1;
@@ -1870,72 +1613,42 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
   float4 xv[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
-    xv[i] = *reinterpret_cast<const float4*>(
-        wl + r * RSI + (DMA ? ln_swz(NL, r, leaf * (LF / 4) + 2 * i + grp) * 16 : (leaf * (LF / 4) + 2 * i + grp) * 16 + leaf * 16));
-  float inv, nmean;
-  v2f_t xl[NI], xh[NI];  // NQK_LN_PK: xv[i] as the pairs (x, y), (z, w), centred in place
-  if constexpr (NQK_LN_PK) {
-    // element pairs as packed f32 (v_pk_add / v_pk_mul: per lane the same IEEE operations in
-    // the same order as the scalar form below, one issue slot for two elements)
+    xv[i] = *reinterpret_cast<const float4*>(wl + r * RSI + ln_swz(NL, r, leaf * (LF / 4) + 2 * i + grp) * 16);
+  // element pairs as packed f32 (v_pk_add / v_pk_mul: per lane the same IEEE operations in
+  // the same order as k_ln_quant_reg's scalar form, one issue slot for two elements)
+  v2f_t xl[NI], xh[NI];  // xv[i] as the pairs (x, y), (z, w), centred in place
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      xl[i] = v2f_t{xv[i].x, xv[i].y};
-      xh[i] = v2f_t{xv[i].z, xv[i].w};
-    }
-    v2f_t al = xl[0], ah = xh[0];
-#pragma unroll
-    for (int i = 1; i < NI; ++i) {
-      al = al + xl[i];
-      ah = ah + xh[i];
-    }
-    float acc = (al[0] + al[1]) + (ah[0] + ah[1]);
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) acc = acc + __shfl_xor(acc, m, 64);
-    nmean = -(acc / (float)COLS);
-    const v2f_t nm2 = v2f_t{nmean, nmean};
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      xl[i] = xl[i] + nm2;
-      xh[i] = xh[i] + nm2;
-    }
-    al = xl[0] * xl[0];
-    ah = xh[0] * xh[0];
-#pragma unroll
-    for (int i = 1; i < NI; ++i) {
-      al = al + xl[i] * xl[i];
-      ah = ah + xh[i] * xh[i];
-    }
-    float v2 = (al[0] + al[1]) + (ah[0] + ah[1]);
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) v2 = v2 + __shfl_xor(v2, m, 64);
-    inv = 1.0f / __builtin_sqrtf(v2 / (float)COLS + eps);
-  } else {
-    float a0 = xv[0].x, a1 = xv[0].y, a2 = xv[0].z, a3 = xv[0].w;
-  #pragma unroll
-    for (int i = 1; i < NI; ++i) {
-      a0 = a0 + xv[i].x; a1 = a1 + xv[i].y; a2 = a2 + xv[i].z; a3 = a3 + xv[i].w;
-    }
-    float acc = (a0 + a1) + (a2 + a3);
-  #pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) acc = acc + __shfl_xor(acc, m, 64);
-    const float fcols = (float)COLS;
-    nmean = -(acc / fcols);
-  #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      xv[i].x = xv[i].x + nmean; xv[i].y = xv[i].y + nmean; xv[i].z = xv[i].z + nmean; xv[i].w = xv[i].w + nmean;
-    }
-    a0 = xv[0].x * xv[0].x; a1 = xv[0].y * xv[0].y; a2 = xv[0].z * xv[0].z; a3 = xv[0].w * xv[0].w;
-  #pragma unroll
-    for (int i = 1; i < NI; ++i) {
-      a0 = a0 + xv[i].x * xv[i].x; a1 = a1 + xv[i].y * xv[i].y;
-      a2 = a2 + xv[i].z * xv[i].z; a3 = a3 + xv[i].w * xv[i].w;
-    }
-    float v2 = (a0 + a1) + (a2 + a3);
-  #pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) v2 = v2 + __shfl_xor(v2, m, 64);
-    const float var = v2 / fcols;
-    inv = 1.0f / __builtin_sqrtf(var + eps);
+  for (int i = 0; i < NI; ++i) {
+    xl[i] = v2f_t{xv[i].x, xv[i].y};
+    xh[i] = v2f_t{xv[i].z, xv[i].w};
   }
+  v2f_t al = xl[0], ah = xh[0];
+#pragma unroll
+  for (int i = 1; i < NI; ++i) {
+    al = al + xl[i];
+    ah = ah + xh[i];
+  }
+  float acc = (al[0] + al[1]) + (ah[0] + ah[1]);
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) acc = acc + __shfl_xor(acc, m, 64);
+  const float nmean = -(acc / (float)COLS);
+  const v2f_t nm2 = v2f_t{nmean, nmean};
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    xl[i] = xl[i] + nm2;
+    xh[i] = xh[i] + nm2;
+  }
+  al = xl[0] * xl[0];
+  ah = xh[0] * xh[0];
+#pragma unroll
+  for (int i = 1; i < NI; ++i) {
+    al = al + xl[i] * xl[i];
+    ah = ah + xh[i] * xh[i];
+  }
+  float v2 = (al[0] + al[1]) + (ah[0] + ah[1]);
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) v2 = v2 + __shfl_xor(v2, m, 64);
+  const float inv = 1.0f / __builtin_sqrtf(v2 / (float)COLS + eps);
   // every lane's tree reads are done before the image is overwritten (in-order LDS)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -1943,19 +1656,13 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
   for (int i = 0; i < NI; ++i) {
     const float4 gg = *reinterpret_cast<const float4*>(g + c0 + 8 * i);
     const float4 bb = *reinterpret_cast<const float4*>(b + c0 + 8 * i);
-    float y[4];
-    if constexpr (NQK_LN_PK) {
-      const v2f_t i2 = v2f_t{inv, inv};
-      const v2f_t yl = ((xl[i] * i2) * v2f_t{gg.x, gg.y}) + v2f_t{bb.x, bb.y};
-      const v2f_t yh = ((xh[i] * i2) * v2f_t{gg.z, gg.w}) + v2f_t{bb.z, bb.w};
-      y[0] = yl[0], y[1] = yl[1], y[2] = yh[0], y[3] = yh[1];
-    } else {
-      y[0] = ((xv[i].x * inv) * gg.x) + bb.x, y[1] = ((xv[i].y * inv) * gg.y) + bb.y;
-      y[2] = ((xv[i].z * inv) * gg.z) + bb.z, y[3] = ((xv[i].w * inv) * gg.w) + bb.w;
-    }
+    const v2f_t i2 = v2f_t{inv, inv};
+    const v2f_t yl = ((xl[i] * i2) * v2f_t{gg.x, gg.y}) + v2f_t{bb.x, bb.y};
+    const v2f_t yh = ((xh[i] * i2) * v2f_t{gg.z, gg.w}) + v2f_t{bb.z, bb.w};
+    const float y[4] = {yl[0], yl[1], yh[0], yh[1]};
     uint32_t packed = 0;
     if constexpr (MQ) {
-      packed = ln_quant4<NQK_LN_PK>(y, rs, mq);
+      packed = ln_quant4<true>(y, rs, mq);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -1982,8 +1689,7 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
 // of a double-buffered image while the current group is reduced, quantized and stored (the
 // single-shot kernel's waves load, then compute, then store: in a grid that is one or a few
 // waves per slot those phases line up across the chip).  gamma / beta stay in registers (a
-// lane's columns are the same in every group).  Same arithmetic as k_ln_quant_lds with
-// NQK_LN_PK / NQK_LN_DMA.
+// lane's columns are the same in every group).  Same arithmetic as k_ln_quant_lds.
 template <int NL, bool MQ>
 __global__ void __launch_bounds__(64)
 k_ln_quant_pers(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
@@ -2104,7 +1810,7 @@ k_ln_quant_pers(const float* __restrict__ x, const float* __restrict__ g, const 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may land after the wave's LDS is released
 }
-constexpr int ln_lds_bytes(int nl, int wpb = 4) { return wpb * (64 / (2 * nl)) * (nl * 96 * 4 + (NQK_LN_DMA ? 0 : nl * 16)); }
+constexpr int ln_lds_bytes(int nl, int wpb = 4) { return wpb * (64 / (2 * nl)) * (nl * 96 * 4); }
 
 // ------------------------------------------------------------------ Softmax + quantize
 // one row per wave; output row stride ldo (>= cols, pad zero-filled); optional row sums
@@ -2193,15 +1899,9 @@ k_transpose_pad(const int8_t* __restrict__ src, int8_t* __restrict__ dst, int64_
 
 using namespace nqk;
 
-// projection GEMM kernel: the 128x256 one; NQK_GEMM_PP=1 selects the ping-pong 256x256
-// one (measured no faster: the k loop is bound by the LDS-DMA latency, not the issue)
-static bool gemm_pingpong() {
-  const char* v = getenv("NQK_GEMM_PP");
-  return v && atoi(v) == 1;
-}
-
+// projection GEMM kernel: the 128x256 one
 template <int EPI, bool I32, bool F32X>
-static void launch_big(bool pp, const int8_t* a, const int8_t* bt, int64_t M, int64_t N, int64_t K, int64_t lda,
+static void launch_big(const int8_t* a, const int8_t* bt, int64_t M, int64_t N, int64_t K, int64_t lda,
                        int64_t ldb, const Epi& e) {
   const int tn = (int)((N + GBN - 1) / GBN);
   if constexpr (EPI == EPI_RESID && !F32X) {
@@ -2224,18 +1924,12 @@ static void launch_big(bool pp, const int8_t* a, const int8_t* bt, int64_t M, in
       return;
     }
   }
-  if (pp) {
-    const int tm = (int)((M + 255) / 256);
-    hipLaunchKernelGGL((k_qgemm_pp<EPI, I32, F32X>), dim3(tm * tn), dim3(512), PP_LDS, stream(), a, bt, (int)M,
-                       (int)N, (int)K, (int)lda, (int)ldb, tm, tn, e);
-  } else {
-    const int tm = (int)((M + 127) / 128);
-    hipLaunchKernelGGL((k_qgemm_big<EPI, I32, F32X>), dim3(tm * tn), dim3(256), BIG_LDS, stream(), a, bt, (int)M,
-                       (int)N, (int)K, (int)lda, (int)ldb, tm, tn, e);
-  }
+  const int tm = (int)((M + 127) / 128);
+  hipLaunchKernelGGL((k_qgemm_big<EPI, I32, F32X>), dim3(tm * tn), dim3(256), BIG_LDS, stream(), a, bt, (int)M,
+                     (int)N, (int)K, (int)lda, (int)ldb, tm, tn, e);
 }
 
-static int g_last_gemm = -1;  // nqk_qgemm_last_kernel: 0 small tiles, 1 big tile, 2 ping-pong, 3 persistent, 4 k_pg,
+static int g_last_gemm = -1;  // nqk_qgemm_last_kernel: 0 small tiles, 1 big tile, (2 retired: ping-pong), 3 persistent, 4 k_pg,
                               // 5 k_pg 256 x 256 (WM = 2), 6 / 7 the same two with the GELU table
 namespace nqk {
 int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, int64_t K, int64_t lda,
@@ -2374,8 +2068,7 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
   const double kk = (double)(params->kdim > K ? params->kdim : K);
   const double bound = 16384.0 * kk + 128.0 * kk * (za + zb) + za * zb * kk;
   const bool i32 = bound < 2147483647.0 * 0.98;
-  const bool pp = gemm_pingpong();
-  const bool big = batch == 1 && (K % (pp ? GBK : GST * GBK)) == 0 && K > 0 && (N % 4) == 0 && params->zp_flags == NQK_ZP_COL &&
+  const bool big = batch == 1 && (K % (GST * GBK)) == 0 && K > 0 && (N % 4) == 0 && params->zp_flags == NQK_ZP_COL &&
                    params->col != nullptr && (epi != EPI_QKV || (params->hdim % 4 == 0 && params->group_cols % 4 == 0)) &&
                    (epi == EPI_QKV || epi == EPI_RESID || epi == EPI_GELU || epi == EPI_NULL);
   // staged epilogue stores 4 columns at once: 16-byte (f32) / 4-byte (int8) aligned outputs
@@ -2393,7 +2086,7 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
     if (!(epi == EPI_RESID && N == 192 && big && aligned && params->ln_gamma && params->ln_beta &&
           (((uintptr_t)params->ln_gamma | (uintptr_t)params->ln_beta) & 15) == 0 && (((uintptr_t)params->ln_out) & 3) == 0 &&
           __builtin_fabsf(params->ln_scale) >= 0x1p-100f && __builtin_fabsf(params->ln_scale) <= 0x1p100f &&
-          !pp && !getenv("NQK_PROJ_RESID")))
+          !getenv("NQK_PROJ_RESID")))
       return fail("nqk_qgemm_fused: a fused LayerNorm needs the residual epilogue at N = 192 on the big-tile path "
                   "(16-byte aligned gamma / beta, a normal ln_scale)");
   }
@@ -2414,11 +2107,10 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
     for (int g = 0; g < ng; ++g) zp_small = zp_small && params->zp_out[g] >= -(1 << 20) && params->zp_out[g] <= (1 << 20);
     const bool f32x = i32 && (epi == EPI_QKV || (epi == EPI_GELU && e.gelu_filter)) && zp_small &&
                       abound + cmax * za < 16777216.0 && !getenv("NQK_NO_F32X");
-    const bool use_pp = pp && !params->b_packed;
+    const bool f32x_r = i32 && epi == EPI_RESID && abound + cmax * za < 16777216.0 && !getenv("NQK_NO_F32X");
     // the persistent 16x16x64 GEMM (nqk_pgemm.hip) where it takes the case (never with a fused
     // LayerNorm: its residual epilogue needs whole 256-column tiles)
     if (params->bt_pg != nullptr && params->ln_out == nullptr) {
-      const bool f32x_r = i32 && epi == EPI_RESID && abound + cmax * za < 16777216.0 && !getenv("NQK_NO_F32X");
       const int rc = pg_launch(epi, a, params->bt_pg, M, N, K, lda, params, f32x || f32x_r);
       if (rc < 0) return rc;
       if (rc > 0) {
@@ -2430,7 +2122,6 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
     // GELU with NQK_PROJ_GELU=1 and the residual epilogues with NQK_PROJ_RESID=1 (faster
     // alone, not inside the two-stream forward, DESIGN.md "Projection GEMM variants");
     // NQK_NO_PROJ=1 keeps the one-tile-per-workgroup kernel everywhere
-    const bool f32x_r = i32 && epi == EPI_RESID && abound + cmax * za < 16777216.0 && !getenv("NQK_NO_F32X");
     const bool proj_shape = params->b_packed && i32 && params->colterm != nullptr && M >= 256 && (M % 256 == 0 || epi != EPI_RESID) && N % GBN == 0 &&
                             (K == 768 || K == 3072) && (double)M * N * 4.0 < 4294967295.0 && (double)M * lda < 4294967295.0 &&
                             !getenv("NQK_NO_PROJ") &&
@@ -2462,15 +2153,15 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
     }
     switch (epi * 3 + (f32x ? 2 : (i32 ? 1 : 0))) {
 #define LB(E) \
-      case E * 3 + 0: launch_big<E, false, false>(use_pp, a, bt, M, N, K, lda, ldb, e); break; \
-      case E * 3 + 1: launch_big<E, true, false>(use_pp, a, bt, M, N, K, lda, ldb, e); break;
+      case E * 3 + 0: launch_big<E, false, false>(a, bt, M, N, K, lda, ldb, e); break; \
+      case E * 3 + 1: launch_big<E, true, false>(a, bt, M, N, K, lda, ldb, e); break;
       LB(EPI_QKV) LB(EPI_RESID) LB(EPI_GELU) LB(EPI_NULL)
 #undef LB
-      case EPI_QKV * 3 + 2: launch_big<EPI_QKV, true, true>(use_pp, a, bt, M, N, K, lda, ldb, e); break;
-      case EPI_GELU * 3 + 2: launch_big<EPI_GELU, true, true>(use_pp, a, bt, M, N, K, lda, ldb, e); break;
+      case EPI_QKV * 3 + 2: launch_big<EPI_QKV, true, true>(a, bt, M, N, K, lda, ldb, e); break;
+      case EPI_GELU * 3 + 2: launch_big<EPI_GELU, true, true>(a, bt, M, N, K, lda, ldb, e); break;
       default: return fail("nqk_qgemm_fused: no big-tile kernel for this epilogue");
     }
-    g_last_gemm = use_pp ? 2 : 1;
+    g_last_gemm = 1;
     return launch_status("nqk_qgemm_fused(big)");
   }
   g_last_gemm = 0;
@@ -2513,9 +2204,9 @@ extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* bet
     const unsigned grid = (unsigned)((lanes + 255) / 256);
     // rows through LDS: linear 1 KiB loads / stores per wave (the LDS-DMA form addresses x by 32-bit
     // buffer offsets: larger inputs take the register-tree kernel)
-    const bool dma_ok = !NQK_LN_DMA || rows * cols * 4 < (int64_t(1) << 31);
+    const bool dma_ok = rows * cols * 4 < (int64_t(1) << 31);
     const char* pe = getenv("NQK_LN_PERS");
-    if (NQK_LN_DMA && dma_ok && pe && atoi(pe) > 0 && mq && !getenv("NQK_LN_REG")) {
+    if (dma_ok && pe && atoi(pe) > 0 && mq && !getenv("NQK_LN_REG")) {
       // persistent double-buffered form: NQK_LN_PERS waves per CU (1-wave workgroups, 24 KiB each)
       const int64_t ngroups = (rows + 32 / p.nleaf - 1) / (32 / p.nleaf);
       const int64_t w = std::min<int64_t>(ngroups, (int64_t)std::min(6, atoi(pe)) * num_cus());

@@ -416,9 +416,6 @@ k_sgemm_mfma(const float* __restrict__ A, const float* __restrict__ B, float* __
 // XCD-aware tile orders (not a constant)
 static int num_xcds() { return xcd_count(); }
 constexpr int EQ_ROW = 20;  // floats per LDS operand row (16 + 4 padding)
-#ifndef NQK_EMBED_PXD
-#define NQK_EMBED_PXD 1
-#endif
 #ifndef NQK_EMBED_DIAG
 #define NQK_EMBED_DIAG 0  // timing diagnostics (wrong results): 1 no k-tile barriers, 2 no A convert, 4 no stores
 #endif
@@ -514,13 +511,10 @@ k_embed_q(const int8_t* __restrict__ q, const float* __restrict__ wt, float* __r
     constexpr int sub = decltype(SUB)::value;
     const int cur = kt & 1;
     const bool more = kt + 1 < NKT;
-    if (more) {
-      load_b(kt + 1);
-      // the next kernel row's image bytes (HBM): NQK_EMBED_PXD 1 = issued at the row's first
-      // k-tile, three k-tiles before their use; 0 = in the k-tile before it
-      if constexpr (NQK_EMBED_PXD == 0 && sub == 2) load_px((kt + 1) / 3, pxn);
-    }
-    if constexpr (NQK_EMBED_PXD == 1 && sub == 0) {
+    if (more) load_b(kt + 1);
+    // the next kernel row's image bytes (HBM): issued at the row's first k-tile, three k-tiles
+    // before their use
+    if constexpr (sub == 0) {
       if (kt + 3 < NKT) load_px(kt / 3 + 1, pxn);
     }
     v4f fa[2][2], fb[WN][2];

@@ -65,9 +65,7 @@ constexpr int PG_TR_ROW = 272;  // bytes per staged residual row (256 + 16: conf
 // waves 4..7 rows 128..255 of the tile, both halves reading the SAME B stage: 32 KiB per k step
 // per CU for 2 x 128 x 256 outputs instead of 2 x 24 KiB (the operand stream measured ~1/3 of
 // FFN-down's time, profiles/r04_pg_operand_probe.txt); the residual transposes get their own LDS
-#ifndef NQK_PG_WM2_RD
-#define NQK_PG_WM2_RD 3  // ring depth of the 256 x 256 form's non-residual instances (4 fits its LDS)
-#endif
+constexpr int NQK_PG_WM2_RD = 3;  // ring depth of the 256 x 256 form's non-residual instances (4 fits its LDS)
 // ring depth: 3 stages, or NQK_PG_WM2_RD for the 256 x 256 form where K is a multiple of 4 k steps
 constexpr int pg_rd(int epi, int wm, int nk) { return (wm == 2 && epi != PG_RESID && nk % 4 == 0) ? NQK_PG_WM2_RD : PG_RD; }
 constexpr int pg_stg(bool b4, int wm = 1) { return (wm ? PG_ASTG * wm : PG_ASTG / 2) + PG_BN * (b4 ? PG_BK / 2 : PG_BK); }
@@ -77,47 +75,24 @@ constexpr int pg_lds_bytes(int epi, bool b4, int wm = 1, int nk = 12) {
          ((b4 || wm == 2) && epi == PG_RESID ? 4 * wm * 16 * PG_TR_ROW : 0);
 }
 
-#ifndef NQK_PG_STAUX
-#define NQK_PG_STAUX 2  // cache-policy bits of the epilogue's output stores: nt (profiles/r03c_*: out-proj
-                        // 77 -> 60 us; 16 = sc1, the line leaves L2: no gain)
-#endif
-#ifndef NQK_PG_STAUX_RESID
-#define NQK_PG_STAUX_RESID 0  // the residual epilogues' f32 output stores: plain, so the LayerNorm that
-                              // reads the rows next finds them in the Infinity Cache (same-box bench A/B,
-                              // profiles/r03_store_policy_ab.txt: LN 46.4 -> 42.1 us, residual GEMMs equal)
-#endif
-#ifndef NQK_PG_RLAUX
-#define NQK_PG_RLAUX -1  // cache-policy bits of the RESID epilogue's residual loads: -1 = nt for K = 3072
-                         // (FFN-down 144 -> 138 us) and plain for K = 768 (nt: out-proj 59 -> 70 us)
-#endif
-#ifndef NQK_PG_RESQ
-#define NQK_PG_RESQ 3  // the residual epilogue's subtiles of residual rows in flight (round 6 A/B: 4)
-#endif
-#ifndef NQK_PG_RDIRECT
-#define NQK_PG_RDIRECT 0  // 1: the residual epilogue straight from the accumulator layout (no LDS transposes),
-                          // so ring slot 2 is free and all three stages of the next tile go out before the
-                          // epilogue's stores (round 6 A/B)
-#endif
-#ifndef NQK_PG_SPREAD
-#define NQK_PG_SPREAD 0  // 1: the stage's LDS-DMA pieces spread over the first half step (A/B variant)
-#endif
-#ifndef NQK_PG_GELU4
-#define NQK_PG_GELU4 1  // GELU epilogue two element pairs at a time, the chains interleaved
-#endif
-#ifndef NQK_PG_NOPK
-#define NQK_PG_NOPK 1  // 1: the QKV epilogue without packed f32 instructions (MI355X_MICROARCH.md:
-                       // beside MFMAs a v_pk_fma_f32 costs more than two v_fma_f32): QKV 97 -> 92 us
-#endif
+// cache-policy bits of the epilogue's output stores: nt (profiles/r03c_*: out-proj 77 -> 60 us;
+// 16 = sc1, the line leaves L2: no gain)
+constexpr int NQK_PG_STAUX = 2;
+// the residual epilogues' f32 output stores: plain, so the LayerNorm that reads the rows next finds
+// them in the Infinity Cache (same-box bench A/B, profiles/r03_store_policy_ab.txt: LN 46.4 -> 42.1 us,
+// residual GEMMs equal)
+constexpr int NQK_PG_STAUX_RESID = 0;
+// cache-policy bits of the RESID epilogue's residual loads: -1 = nt for K = 3072 (FFN-down
+// 144 -> 138 us) and plain for K = 768 (nt: out-proj 59 -> 70 us)
+constexpr int NQK_PG_RLAUX = -1;
+constexpr int NQK_PG_RESQ = 3;  // the residual epilogue's subtiles of residual rows in flight (round 6 A/B: 4)
 
-#ifndef NQK_PG_PRIO
-#define NQK_PG_PRIO 3  // 3: s_setprio 1 in the epilogue, 0 in the k loop (the epilogue's VALU ahead of the
-                       // other workgroup's k loop on the SIMD: -2..-4 %, profiles/r03c_*); 1: the reverse;
-                       // 2: static prio 1 for the second workgroup of a CU; 0: none
-#endif
 #ifndef NQK_PG_DIAG
 #define NQK_PG_DIAG 0  // diagnostic builds only (tools/pg_diag.sh): 1 = no epilogue stores,
                        // 2 = trivial epilogue math, 4 = no operand loads, 8 = no barriers,
-                       // 16 = no fragment reads, 4096 = no residual loads (zeros)
+                       // 16 = no fragment reads, 32 = no exact fallback, 128 = no B pieces,
+                       // 256 = no A pieces, 512 = the A pieces as whole cache lines, 4096 = no residual
+                       // loads (zeros), 8192 = the QKV stores to one address
 #endif
 
 // physical 16-B chunk of logical chunk c in 64-B LDS row r is c ^ pg_sw(r): the 16 lanes of
@@ -156,19 +131,10 @@ __device__ __forceinline__ v4i pg_lds16(const void* p) {
 }
 // ds_read_b128 at base + a compile-time byte offset (the instruction's 16-bit offset field:
 // one address VGPR for every fragment read of the loop)
-#ifndef NQK_PG_ASMREAD
-#define NQK_PG_ASMREAD 0  // diagnostic: fragment reads by inline asm
-#endif
 template <int OFF>
 __device__ __forceinline__ v4i pg_lds16o(const int8_t* base) {
-  static_assert(OFF >= 0 && (OFF < 65536 || !NQK_PG_ASMREAD), "ds_read offset");
-  if constexpr (NQK_PG_ASMREAD) {
-    v4i v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"((uint32_t)(uintptr_t)(lds_ptr_t)base), "n"(OFF));
-    return v;
-  } else {
-    return *reinterpret_cast<const v4i*>(base + OFF);  // the offset folds into the instruction
-  }
+  static_assert(OFF >= 0, "ds_read offset");
+  return *reinterpret_cast<const v4i*>(base + OFF);  // the offset folds into the instruction
 }
 // ds_read_b64 at base + a compile-time byte offset (the int4 weight fragments)
 template <int OFF>
@@ -291,7 +257,7 @@ __device__ __forceinline__ void pg_exact_fix1(int q, const int (&av)[16], const 
 // a loop that is not unrolled (av / xv / pk indexed by the wave-uniform q stay in VGPRs via
 // relative moves), so the long exact chain is not duplicated per element and per step; QKV:
 // unrolled (its exact chain is short; measured faster, profiles/r03_pg_micro.txt).
-// gm (QKV, and GELU with NQK_PG_GELU4): bit g set when some lane's filter measure of elements
+// gm (QKV and GELU): bit g set when some lane's filter measure of elements
 // 4 g .. 4 g + 3 failed; the other groups are skipped (their elements all passed)
 template <int EPI>
 __device__ __forceinline__ void pg_exact_fix(const int (&av)[16], const float (&xv)[16], uint32_t (&pk)[4],
@@ -367,12 +333,8 @@ constexpr float PG_QLIM = 0x1.fffffcp-2f;
 // QKV filter margin (round 4): |u - t| <= 6 units (2^-24) of |v c1| + 5 of |c2| to first order —
 // the roundings of c1 = RN(sacc rsf), rsf = RN(1/s) and the fma on the fast side, of v sacc,
 // + bias and / s_out on the reference's — so 6.25 and 5.25 units (round 3 used 8 and 16)
-#ifndef NQK_PG_QK1
-#define NQK_PG_QK1 0x1.9p-22f  // 6.25 2^-24 per |v c1|
-#endif
-#ifndef NQK_PG_QKC2
-#define NQK_PG_QKC2 0x1.5p-22f  // 5.25 2^-24 per |c2|
-#endif
+constexpr float NQK_PG_QK1 = 0x1.9p-22f;   // 6.25 2^-24 per |v c1|
+constexpr float NQK_PG_QKC2 = 0x1.5p-22f;  // 5.25 2^-24 per |c2|
 
 
 // B4: int4 weights (every value in [-8, 7]) as the nibble image of nqk_pack_pg4: a stage's
@@ -424,7 +386,7 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   // walk the band [lo, hi) of tile ids, every nx-th tile from lo + jx; tile ids are
   // row-panel major, so the tiles in flight on an XCD share A row panels in its L2.
   const XcdWalk xw = xcd_walk((int)blockIdx.x, (int)gridDim.x, ntiles, e.xcds);  // nqk_xcd.h
-  const int G = gridDim.x, first = xw.first, nx = xw.step, iters = xw.iters;
+  const int first = xw.first, nx = xw.step, iters = xw.iters;
   if (iters == 0) return;
   auto tile_at = [&](int it) { return first + (it < iters ? it : iters - 1) * nx; };
 
@@ -695,11 +657,10 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
         }
         uint32_t pk[4] = {0, 0, 0, 0};
         uint32_t worst = 0;
-        uint32_t wgr[4] = {0, 0, 0, 0};  // QKV, GELU4: the measure's maximum per group of 4 elements
+        uint32_t wgr[4] = {0, 0, 0, 0};  // the measure's maximum per group of 4 elements
         float hv[16];
-        v2f sprev;
-        // GELU, two pairs at a time (NQK_PG_GELU4): the two chains interleaved
-        if constexpr (EPI == PG_GELU && NQK_PG_GELU4 && (NQK_PG_DIAG & 2) == 0) {
+        // GELU, two pairs at a time: the two chains interleaved
+        if constexpr (EPI == PG_GELU && (NQK_PG_DIAG & 2) == 0) {
 #pragma unroll
           for (int q = 0; q < 16; q += 4) {
             const v4i& av4 = acc[i][q >> 2];
@@ -726,53 +687,30 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
             pk[q >> 2] = pack4_low(s0, s1);
           }
         }
-        // the fast paths on element pairs (packed f32 arithmetic where an instruction exists)
+        // QKV (alone: GELU takes the form above) on element pairs, without packed f32 instructions
+        // (MI355X_MICROARCH.md: beside MFMAs a v_pk_fma_f32 costs more than two v_fma_f32; the same
+        // IEEE operations per element: QKV 97 -> 92 us)
+        if constexpr (EPI == PG_QKV) {
 #pragma unroll
-        for (int q = 0; q < 16 && (NQK_PG_DIAG & 2) == 0 && !(EPI == PG_GELU && NQK_PG_GELU4); q += 2) {
-          const v2f vf = v2f{(float)acc[i][q >> 2][q & 3], (float)acc[i][q >> 2][(q & 3) + 1]};
-          v2f dd, sv;
-          float m0, m1;
-          if constexpr (EPI == PG_QKV) {  // (pg_round2 measured slower here: a longer dependent chain)
-            v2f u, rr, b;
-            if constexpr (NQK_PG_NOPK) {  // the same IEEE operations per element, unpacked
+          for (int q = 0; q < 16 && (NQK_PG_DIAG & 2) == 0; q += 2) {
+            // (pg_round2 measured slower here: a longer dependent chain)
+            const v2f vf = v2f{(float)acc[i][q >> 2][q & 3], (float)acc[i][q >> 2][(q & 3) + 1]};
+            v2f dd, b;
 #pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                u[j] = __builtin_fmaf(vf[j], c1, c2[q + j]);
-                rr[j] = __builtin_rintf(u[j]);
-                dd[j] = u[j] - rr[j];
-                b[j] = rr[j] + zp128;
-              }
-            } else {
-              u = __builtin_elementwise_fma(vf, v2f{c1, c1}, v2f{c2[q], c2[q + 1]});
-              rr = v2f{__builtin_rintf(u[0]), __builtin_rintf(u[1])};
-              dd = u - rr;
-              b = rr + v2f{zp128, zp128};
+            for (int j = 0; j < 2; ++j) {
+              const float u = __builtin_fmaf(vf[j], c1, c2[q + j]);
+              const float rr = __builtin_rintf(u);
+              dd[j] = u - rr;
+              b[j] = rr + zp128;
             }
-            m0 = __builtin_fmaf(__builtin_fabsf(vf[0]), k1, __builtin_fabsf(dd[0]));
-            m1 = __builtin_fmaf(__builtin_fabsf(vf[1]), k1, __builtin_fabsf(dd[1]));
+            const float m0 = __builtin_fmaf(__builtin_fabsf(vf[0]), k1, __builtin_fabsf(dd[0]));
+            const float m1 = __builtin_fmaf(__builtin_fabsf(vf[1]), k1, __builtin_fabsf(dd[1]));
             pk[q >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(S8 ? b[0] : __builtin_amdgcn_fmed3f(b[0], e.blo, e.bhi), q & 3,
                                                         pk[q >> 2]);
             pk[q >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(S8 ? b[1] : __builtin_amdgcn_fmed3f(b[1], e.blo, e.bhi),
                                                         (q & 3) + 1, pk[q >> 2]);
-          } else {  // GELU: h exactly as the reference (F32X), then the filtered fast chain
-            const v2f h = v2f{bias[q], bias[q + 1]} + vf * v2f{sacc, sacc};
-            hv[q] = h[0];
-            hv[q + 1] = h[1];
-            const v2f tf = gelu_fast2(h) * v2f{rsf, rsf};
-            sv = round_magic2(tf, qlo, qhi, magic, dd);
-            m0 = __builtin_fmaf(__builtin_fabsf(h[0]), e.g_rel, __builtin_fabsf(dd[0]));
-            m1 = __builtin_fmaf(__builtin_fabsf(h[1]), e.g_rel, __builtin_fabsf(dd[1]));
-          }
-          if constexpr (EPI == PG_QKV)
             wgr[q >> 2] = __builtin_elementwise_max(wgr[q >> 2], __builtin_elementwise_max(__float_as_uint(m0), __float_as_uint(m1)));
-          else
-            worst = __builtin_elementwise_max(worst, __builtin_elementwise_max(__float_as_uint(m0), __float_as_uint(m1)));
-          if constexpr (EPI != PG_QKV) {
-            if (q & 2) pk[q >> 2] = pack4_low(sprev, sv);
-            sprev = sv;
           }
-        }
-        if constexpr (EPI == PG_QKV) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) pk[g] ^= 0x80808080u;  // offset bytes to two's complement
           worst = __builtin_elementwise_max(__builtin_elementwise_max(wgr[0], wgr[1]),
@@ -791,7 +729,7 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
               xv[q] = EPI == PG_QKV ? bias[q] : hv[q];
             }
             uint32_t gm = 15u;
-            if constexpr (EPI == PG_QKV || (EPI == PG_GELU && NQK_PG_GELU4)) {
+            if constexpr (EPI == PG_QKV || EPI == PG_GELU) {
               gm = 0u;
 #pragma unroll
               for (int g = 0; g < 4; ++g) gm |= __any(wgr[g] >= __float_as_uint(lim)) ? 1u << g : 0u;
@@ -820,62 +758,20 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   int8_t* const tr = lds + (B4 || WM == 2 ? COLP + 4096 : 2 * STG) + wave * (16 * TR_ROW);
   const int ta = lane & 15, tb = lane >> 4;
   constexpr int RQ = NQK_PG_RESQ;  // residual subtiles in flight (register slots)
-  // DIRECT (NQK_PG_RDIRECT): no transposes, ring slot 2 stays free, PRE = the last stage of the next
-  // tile issued before this tile's epilogue (RD - 2 otherwise)
-  constexpr bool DIRECT = RESID && NQK_PG_RDIRECT && !B4 && WM == 1 && !RB;
-  constexpr int PRE = DIRECT ? RD - 1 : RD - 2;
+  // (straight from the accumulator layout, no LDS transposes, so that ring slot 2 is free and all
+  // three stages of the next tile go out before the epilogue's stores: round 6 A/B, not kept)
+  constexpr int PRE = RD - 2;  // stages of the next tile issued before this tile's epilogue
   v4u resv[RQ][4];
   auto res_off = [&](const Src& s, int i, int k) __attribute__((always_inline)) {
     return (uint32_t)(((s.r0 + PG_BM * wm + 16 * i + 4 * k + tb) * e.ldo + s.tn * PG_BN + 64 * wn + 4 * ta) * 4);
-  };
-  // DIRECT: lane (l15, lg) of subtile i, column block j: row 16 i + l15, columns 16 j + 4 lg .. + 3 of
-  // the wave's 64 — the accumulator layout itself (16 rows x 64 B per instruction)
-  auto res_off_d = [&](const Src& s, int i, int j) __attribute__((always_inline)) {
-    return (uint32_t)(((s.r0 + PG_BM * wm + 16 * i + l15) * e.ldo + s.tn * PG_BN + 64 * wn + 16 * j + 4 * lg) * 4);
   };
   auto res_issue = [&](const Src& s, auto I) __attribute__((always_inline)) {
     constexpr int i = decltype(I)::value;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       resv[i % RQ][k] = pg_load16(s.tn * PG_BN + 64 * wn < N && (NQK_PG_DIAG & 4096) == 0 ? r_res : r_nul,
-                                 DIRECT ? res_off_d(s, i, k) : res_off(s, i, k), 0u,
+                                 res_off(s, i, k), 0u,
                                  NQK_PG_RLAUX >= 0 ? NQK_PG_RLAUX : (NK == 48 ? 2 : 0));
-  };
-  auto epilogue_resid_direct = [&](const Src& s, int cslot) __attribute__((always_inline)) {
-    const int8_t* cp = lds + COLP + cslot * 2048;
-    v4i bj[4];  // bias of columns 16 j + 4 lg .. + 3
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bj[j] = pg_lds16(cp + 1024 + (64 * wn + 16 * j + 4 * lg) * 4);
-    const rsrc_t r_out = pg_rsrc(e.out[0], s.tn * PG_BN + 64 * wn < N ? (uint32_t)((uint64_t)M * e.ldo * 4) : 0u);
-    const float sacc = e.sacc[0];
-    sfor<0, 8>([&](auto I) __attribute__((always_inline)) {
-      constexpr int i = decltype(I)::value;
-      const v4u(&rv)[4] = resv[i % RQ];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const v4i t = acc[i][j];
-        const v4i bb = bj[j];
-        v4u st;
-        if constexpr (F32X) {
-          const v2f b01 = v2f{__int_as_float(bb[0]), __int_as_float(bb[1])};
-          const v2f b23 = v2f{__int_as_float(bb[2]), __int_as_float(bb[3])};
-          const v2f d01 = v2f{(float)t[0], (float)t[1]} * v2f{sacc, sacc};
-          const v2f d23 = v2f{(float)t[2], (float)t[3]} * v2f{sacc, sacc};
-          const v2f y01 = (b01 + d01) + v2f{__uint_as_float(rv[j][0]), __uint_as_float(rv[j][1])};
-          const v2f y23 = (b23 + d23) + v2f{__uint_as_float(rv[j][2]), __uint_as_float(rv[j][3])};
-          st = v4u{__float_as_uint(y01[0]), __float_as_uint(y01[1]), __float_as_uint(y23[0]), __float_as_uint(y23[1])};
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float d = (float)((double)t[r] * (double)sacc);
-            st[r] = __float_as_uint((__int_as_float(bb[r]) + d) + __uint_as_float(rv[j][r]));
-          }
-        }
-        if constexpr ((NQK_PG_DIAG & 1) != 0) asm volatile("" ::"v"(st[0] ^ st[1] ^ st[2] ^ st[3]));
-        else __builtin_amdgcn_raw_buffer_store_b128(st, r_out, res_off_d(s, i, j), 0, NQK_PG_STAUX_RESID);
-      }
-      if constexpr (i + RQ - 1 < 8) res_issue(s, ic<i + RQ - 1>{});
-    });
   };
   auto epilogue_resid = [&](const Src& s, int cslot) __attribute__((always_inline)) {
     const int8_t* cp = lds + COLP + cslot * 2048;
@@ -947,7 +843,9 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
     issue_colp(cur.tn, 0);
     issue_a(cur);
     for (int it = 0; it < iters; ++it) {
-      if constexpr (NQK_PG_PRIO == 3) __builtin_amdgcn_s_setprio(0);
+      // s_setprio 0 in the k loop, 1 in the epilogue: the epilogue's VALU ahead of the other
+      // workgroup's k loop on the SIMD (-2..-4 %, profiles/r03c_*)
+      __builtin_amdgcn_s_setprio(0);
       const bool more = it + 1 < iters;
       const Src nxt = src_of(tile_at(more ? it + 1 : it));
       const int cs = it & 1;
@@ -994,7 +892,7 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
       issue_colp(nxt.tn, cs ^ 1);
       issue_a(nxt);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (NQK_PG_PRIO == 3) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       epilogue(cur, cs);
       cur = nxt;
     }
@@ -1008,12 +906,8 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   if constexpr (pg_is_glut(EPI)) pg_dma16(pg_rsrc(e.lut, e.lut_bytes), lds + LUTO + wave * 1024, 16 * lane, 1024u * wave);
   issue_colp(cur.tn, 0);
   sfor<0, PRE + 1>([&](auto S) __attribute__((always_inline)) { issue_stage(cur, decltype(S)::value, decltype(S)::value); });
-  if constexpr (NQK_PG_PRIO == 2) {
-    if ((int)blockIdx.x >= G / 2) __builtin_amdgcn_s_setprio(1);
-  }
   for (int it = 0; it < iters; ++it) {
-    if constexpr (NQK_PG_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-    if constexpr (NQK_PG_PRIO == 3) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);  // (k loop 0, epilogue 1: as above)
     const bool more = it + 1 < iters;
     const Src nxt = src_of(tile_at(more ? it + 1 : it));
     const int cs = it & 1;
@@ -1090,16 +984,8 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
       half(ic<0>{}, std::integral_constant<bool, kt == 0>{}, a_lo, bc, cinit, [&](auto Q) __attribute__((always_inline)) {
         constexpr int q = decltype(Q)::value;
         if constexpr (q < 4) rd_a(a_hi, ic<slot>{}, ic<4>{}, Q);
-        // stage kt + 2: NQK_PG_SPREAD 0 = all pieces after MFMA 4; 1 = one piece every
-        // other MFMA from MFMA 1 (a burst of LDS-DMA issues costs each piece more:
-        // MI355X_MICROARCH.md, LDS-DMA piece issue cost)
-        if constexpr (kt + RD - 1 < NK && kt + RD - 1 > PRE) {
-          if constexpr (NQK_PG_SPREAD == 0) {
-            if constexpr (q == 4) issue_stage(cur, kt + RD - 1, (kt + RD - 1) % RD);
-          } else if constexpr ((q & 1) == 1 && (q >> 1) < PW) {
-            issue_piece(cur, kt + RD - 1, (kt + RD - 1) % RD, q >> 1);
-          }
-        }
+        // stage kt + 2: all pieces after MFMA 4
+        if constexpr (kt + RD - 1 < NK && kt + RD - 1 > PRE && q == 4) issue_stage(cur, kt + RD - 1, (kt + RD - 1) % RD);
       });
       if constexpr (kt == 1) issue_colp(nxt.tn, cs ^ 1);
       if constexpr (kt + 1 < NK) {
@@ -1138,16 +1024,14 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
     // VMEM counts stay the same on every path)
     sfor<0, PRE + 1>([&](auto S) __attribute__((always_inline)) { issue_stage(nxt, decltype(S)::value, decltype(S)::value); });
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (NQK_PG_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-    if constexpr (NQK_PG_PRIO == 3) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     if constexpr (B4) {  // the MFMAs accumulated 16 acc
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] >> 4;
     }
-    if constexpr (DIRECT) epilogue_resid_direct(cur, cs);
-    else if constexpr (RESID) epilogue_resid(cur, cs);
+    if constexpr (RESID) epilogue_resid(cur, cs);
     else epilogue(cur, cs);
     cur = nxt;
   }

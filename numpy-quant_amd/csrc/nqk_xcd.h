@@ -17,7 +17,7 @@
 
 namespace nqk {
 
-// One tile per workgroup (k_embed_q, k_embed_q16, k_qgemm_big / k_qgemm_pp): workgroup b of T
+// One tile per workgroup (k_embed_q, k_embed_q16, k_qgemm_big): workgroup b of T
 // takes tile xcd_remap(b, T, XC).  Band x holds T / XC tiles, one more in the first T % XC
 // bands — exactly the number of workgroups b < T with b % XC == x, whose b / XC counts them.
 template <typename I>

@@ -238,32 +238,32 @@ def pv_ties_case():
 
 # ------------------------------------------------------------------------------- case lists
 C = GemmCase
-_FB = ["epi", "big", "pp", "pg_fb", "proj_fb"]   # *_fb: the persistent kernels are offered the case and must decline it
-_F32 = ["epi", "big", "pp", "pg", "proj"]
+_FB = ["epi", "big", "pg_fb", "proj_fb"]   # *_fb: the persistent kernels are offered the case and must decline it
+_F32 = ["epi", "big", "pg", "proj"]
 
 # every route at the smallest shapes that reach it (input 4: random data, small output scales)
 ROUTE_CASES = [
-    (C("qkv", 131, 192, 192, "small"), ["epi", "big", "big_pack", "pp", "pg", "pg64"]),
-    (C("qkv", 197 * 3, 576, 192, "small"), ["epi", "big", "big_pack", "pp", "pg", "pg64"]),
+    (C("qkv", 131, 192, 192, "small"), ["epi", "big", "big_pack", "pg", "pg64"]),
+    (C("qkv", 197 * 3, 576, 192, "small"), ["epi", "big", "big_pack", "pg", "pg64"]),
     # (k_proj takes whole images only, M % tokens == 0: it must decline the partial last image, proj_fb)
-    (C("qkv", 300, 768, 768, "small"), ["epi", "big", "big_pack", "pp", "proj_fb", "pg", "pg_wm2"]),
+    (C("qkv", 300, 768, 768, "small"), ["epi", "big", "big_pack", "proj_fb", "pg", "pg_wm2"]),
     (C("qkv", 256 + 77, 2304, 768, "small"), ["big", "proj_fb", "pg", "pg_wm2"]),
     (C("qkv", 197 * 2, 768, 768, "small"), ["big", "proj", "pg_wm2"]),
     (C("qkv", 197 * 2, 2304, 768, "small"), ["proj", "pg"]),
-    (C("qkv", 197 * 3, 576, 3072, "small"), ["epi", "big", "pp"]),
-    (C("resid", 131, 768, 192), ["epi", "big", "big_pack", "pp", "pg"]),
-    (C("resid", 300, 768, 768), ["epi", "big", "big_pack", "pp", "pg", "pg_wm2"]),
+    (C("qkv", 197 * 3, 576, 3072, "small"), ["epi", "big"]),
+    (C("resid", 131, 768, 192), ["epi", "big", "big_pack", "pg"]),
+    (C("resid", 300, 768, 768), ["epi", "big", "big_pack", "pg", "pg_wm2"]),
     (C("resid", 512, 768, 768), ["proj", "pg_wm2"]),
     (C("resid", 256 + 77, 768, 3072, l1=True), ["big", "pg", "pg_wm2"]),
     (C("resid", 256, 768, 3072, l1=True), ["proj", "pg"]),
     (C("resid", 131, 3072, 192), ["big", "pg"]),
-    (C("gelu", 131, 768, 192), ["epi", "big", "big_pack", "pp", "pg", "pg64", "glut"]),
-    (C("gelu", 300, 3072, 768, "small"), ["big", "big_pack", "pp", "proj", "pg", "pg_wm2", "glut", "glut_wm2"]),
+    (C("gelu", 131, 768, 192), ["epi", "big", "big_pack", "pg", "pg64", "glut"]),
+    (C("gelu", 300, 3072, 768, "small"), ["big", "big_pack", "proj", "pg", "pg_wm2", "glut", "glut_wm2"]),
     (C("gelu", 197 * 3, 768, 768, "small"), ["epi", "pg", "glut"]),
     # s_out = 0.0008: the increasing branch alone needs > 1024 buckets of 0.885 s, so nqk_gelu_lut_build
     # returns n = 0; zp_out = 100 keeps the negative half of the GELU outputs unclipped
     (C("gelu", 300, 768, 768, "tiny", zpo="p100"), ["nolut"]),
-    (C("gelu", 131, 2304, 3072), ["big", "pp"]),
+    (C("gelu", 131, 2304, 3072), ["big"]),
 ]
 # input 3: bit widths, output zero points, zpa
 for _bw in (2, 3):
@@ -282,22 +282,22 @@ for _e, _m in (("qkv", 197 * 2), ("gelu", 300)):  # QKV: two whole images (k_pro
 for _e, _m in (("qkv", 197 * 2), ("gelu", 300), ("resid", 300)):
     for _z in (0, -128, 127):
         ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=_z), ["epi", "big", "pg"] + (["proj"] if _e != "resid" else [])))
-    ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=1 << 20), ["epi", "big", "big_pack", "pp"]))
+    ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=1 << 20), ["epi", "big", "big_pack"]))
 
 # input 1: accumulators at the f32-exactness bound, just below 2^24 and just above
 EXTREME_CASES = []
 for _z in (40, 43, 140):  # K = 768 without col_l1max: 2^14 K + 128 K zpa = 16 515 072 / 16 809 984 / 26 345 472
     _lo = _z == 40
-    EXTREME_CASES += [(C("qkv", 131, 576, 768, "extreme", zpa=_z), ["epi", "big", "pp", "pg" if _lo else "pg_fb"]),
-                      (C("gelu", 131, 768, 768, "extreme", zpa=_z), ["epi", "big", "pp", "pg" if _lo else "pg_fb"]),
+    EXTREME_CASES += [(C("qkv", 131, 576, 768, "extreme", zpa=_z), ["epi", "big", "pg" if _lo else "pg_fb"]),
+                      (C("gelu", 131, 768, 768, "extreme", zpa=_z), ["epi", "big", "pg" if _lo else "pg_fb"]),
                       (C("resid", 256, 768, 768, "extreme", zpa=_z), ["big", "pg", "pg_wm2", "proj"])]
 for _z in (2, 3):  # K = 3072 with col_l1max = 42 K: 128 L + L zpa = 16 773 120 / 16 902 144
     EXTREME_CASES += [(C("resid", 256, 768, 3072, "extreme", zpa=_z, l1=True), ["big", "pg", "pg_wm2", "proj"]),
-                      (C("qkv", 131, 576, 3072, "extreme", zpa=_z, l1=True), ["big", "pp"]),
-                      (C("gelu", 131, 768, 3072, "extreme", zpa=_z, l1=True), ["big", "pp"])]
+                      (C("qkv", 131, 576, 3072, "extreme", zpa=_z, l1=True), ["big"]),
+                      (C("gelu", 131, 768, 3072, "extreme", zpa=_z, l1=True), ["big"])]
 
 # input 2: exact ties
-TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "pp", "pg", "pg64"]),
+TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "pg", "pg64"]),
               (C("qkv", 197 * 2, 768, 768, "ties"), ["big", "pg", "pg_wm2", "proj"])]
 
 # the fused LayerNorm of k_qgemm_big at N = 192: bit widths, ln_zp at +-2^20 (magic-number quantize) and beyond (f64)

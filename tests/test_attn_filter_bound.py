@@ -1,6 +1,7 @@
-"""The attention's P-quantize filter margins (nqk_attn.hip NQK_ATTN_PM_R / NQK_ATTN_PM_T /
-NQK_ATTN_PKL), restated in NumPy f32 arithmetic and checked on elements placed next to rounding
-boundaries: whenever the fast path's measure passes its limit, its byte equals the reference
+"""The attention's P-quantize filter margins (nqk_attn.hip, the constants NQK_ATTN_PM_R and
+NQK_ATTN_PM_T; the pkl cases are the two-term product tf = RN(e kpf + RN(e kpl)) with its margin
+3.125 u, an A/B variant that the kernel no longer carries), restated in NumPy f32 arithmetic and
+checked on elements placed next to rounding boundaries: whenever the fast path's measure passes its limit, its byte equals the reference
 chain's (numpy_helper.py softmax, then numpy_quantization.py:24-34 quantize:
 t = RN(RN(e / tot) / s_p), q = rint(clip(zp + t, lo, hi))).  A margin below the proven bound
 must show mismatches on the same inputs, so the check has teeth."""

@@ -175,8 +175,8 @@ def test_embed_q_equals_patchify_then_sgemm_embed(n, h, w, N, zp, mfma, monkeypa
     np.testing.assert_array_equal(out.to_host().view(np.int32), ref.to_host().view(np.int32))
 
 
-_VARIANTS = [{}, {"NQK_GEMM_PP": "1"}, {"NQK_NO_F32X": "1"}, {"NQK_NO_F32X": "1", "NQK_GEMM_PP": "1"},
-             {"NQK_NO_GELU_FILTER": "1", "NQK_NO_F32X": "1"}, {"PACK": "1"}, {"PACK": "1", "NQK_NO_F32X": "1"}]
+_VARIANTS = [{}, {"NQK_NO_F32X": "1"}, {"NQK_NO_GELU_FILTER": "1", "NQK_NO_F32X": "1"}, {"PACK": "1"},
+             {"PACK": "1", "NQK_NO_F32X": "1"}]
 
 
 @pytest.mark.parametrize("epi_name,M,N,K,zpa,s_out,zp", [
@@ -191,7 +191,7 @@ _VARIANTS = [{}, {"NQK_GEMM_PP": "1"}, {"NQK_NO_F32X": "1"}, {"NQK_NO_F32X": "1"
 ])
 def test_projection_gemm_variants_agree(epi_name, M, N, K, zpa, s_out, zp, monkeypatch):
     """Projection GEMM variants: the 128x256 kernel (k_qgemm_big) with row-major or
-    tile-packed weights (nqk_pack_b), the ping-pong 256x256 kernel (k_qgemm_pp), f64 or
+    tile-packed weights (nqk_pack_b), f64 or
     proven-exact f32 epilogue arithmetic with rounding filters,
     GELU filter on or off -- all bit-identical, on ragged tiles and small output scales
     that put many values next to rounding boundaries.  The exact-chain variant is itself
@@ -215,7 +215,7 @@ def test_projection_gemm_variants_agree(epi_name, M, N, K, zpa, s_out, zp, monke
     for var in _VARIANTS:
         if "PACK" in var and packed is None:
             continue
-        for k in ("NQK_GEMM_PP", "NQK_NO_F32X", "NQK_NO_GELU_FILTER"):
+        for k in ("NQK_NO_F32X", "NQK_NO_GELU_FILTER"):
             monkeypatch.delenv(k, raising=False)
         for k, v in var.items():
             if k != "PACK":

@@ -23,7 +23,7 @@ import _fused_cases as F
 pytestmark = pytest.mark.gpu
 
 _SWITCHES = ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID", "NQK_PROJ_RESID", "NQK_PROJ_GELU", "NQK_PG_WM",
-             "NQK_PG_WM0", "NQK_GEMM_PP", "NQK_NO_GELU_FILTER", "NQK_NO_GLUT", "NQK_GLUT_NO1", "NQK_GLUT_NOWIDE", "NQK_NO_L1",
+             "NQK_PG_WM0", "NQK_NO_GELU_FILTER", "NQK_NO_GLUT", "NQK_GLUT_NO1", "NQK_GLUT_NOWIDE", "NQK_NO_L1",
              "NQK_PROJ_CUS", "NQK_LN_F64Q", "NQK_PG_RB", "NQK_PG_WGPC", "NQK_NO_BPACK", "NQK_NO_B4", "NQK_XCDS",
              "NQK_PG_NOS8")
 _PG = {"NQK_NO_PROJ": "1", "NQK_PG_WM": "1"}
@@ -34,7 +34,6 @@ ROUTES = {
     "big": (1, {"NQK_NO_PROJ": "1"}, "plain", None, False),
     "big_pack": (1, {"NQK_NO_PROJ": "1"}, "pack", None, False),
     "big_pack4": (1, {"NQK_NO_PROJ": "1"}, "pack4", None, False),
-    "pp": (2, {"NQK_NO_PROJ": "1", "NQK_GEMM_PP": "1"}, "plain", None, False),
     "proj": (3, _PROJ, "pack", None, False),
     "proj8": (3, dict(_PROJ, NQK_PROJ_CUS="8"), "pack", None, False),
     "proj_fb": (1, _PROJ, "pack", None, False),              # offered to k_proj, which must decline

@@ -363,7 +363,7 @@ def test_ln_magic_quantize_equals_f64_chain(bw):
 
 
 def test_ln_dma_swizzle_conflict_free():
-    """k_ln_quant_lds with NQK_LN_DMA (nqk_fused.hip ln_swz): the row image loaded by LDS-DMA is
+    """k_ln_quant_lds (nqk_fused.hip ln_swz): the row image loaded by LDS-DMA is
     XOR-swizzled so that the tree reads (lane (row, leaf, grp) reads 16-B chunk 24 leaf + 2 i + grp
     of its row) put the 16 lanes of every ds_read_b128 lane group (MI355X_MICROARCH.md, LDS table)
     on 16 different 4-bank slots, for 8, 4 and 2 leaves; the swizzle is a permutation of each row

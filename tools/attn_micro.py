@@ -3,7 +3,7 @@
 build and, side by side in ONE process (interleaved rounds; MI355X_MICROARCH.md: never rank
 builds timed in different processes), any diagnostic builds:
 
-  AM_LIBS=name=path,...   extra builds (tools/gemm_diag.sh with SRC=nqk_attn)
+  AM_LIBS=name=path,...   extra builds (tools/diag_build.sh)
   AM_ROUNDS, AM_REPS      interleaved rounds, launches per timing"""
 import ctypes
 import os

@@ -2,9 +2,8 @@
 """The fused attention on the bench's own data (round 4): builds and calibrates the ViT-Base
 model exactly as bench.py does, runs one B = 256 forward, then times nqk_attention_fused on
 the last layer's Q / K / V (still in the plan's workspace) with that layer's quantization
-parameters — for the main build and, side by side in one process, diagnostic builds
-(AM_LIBS=name=path,...).  A build with NQK_ATTN_DIAG & 128 also reports how many wave-tiles
-took each slow path (nqk_attn_diag_stats)."""
+parameters — for the main build and, side by side in one process, variant builds
+(AM_LIBS=name=path,..., tools/diag_build.sh)."""
 import ctypes
 import os
 import sys
@@ -110,15 +109,4 @@ for _ in range(ROUNDS):
 for n, ts in res.items():
     print(f"attention[{n}] (bench data, last layer, B={B}): min {min(ts):.1f} us  med {sorted(ts)[len(ts) // 2]:.1f} us",
           flush=True)
-    fn = getattr(libs.get(n), "nqk_attn_diag_stats", None)
-    if fn is not None:
-        st = (ctypes.c_ulonglong * 4)()
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        fn(st, 1)
-        libs[n].nqk_attention_fused(q.vp, k.vp, v.vp, ctx.vp, B * H, ctypes.byref(a))
-        libs[n].nqk_sync()
-        fn(st, 1)
-        tiles = B * H * 7 * 7  # wave-tiles x score tiles per launch (P counters count per score tile)
-        print(f"  one launch: clamped-exp wave-tiles {st[0]}, clamped-P {st[1]} (of {B * H * 7} wave row tiles); "
-              f"P exact fallbacks {st[2]} (of {tiles} score tiles); context fallbacks {st[3]}", flush=True)
 group.close()

@@ -3,7 +3,7 @@
 # PGM_LIBS=...): each argument name=FILES:FLAGS recompiles the listed sources (comma-separated,
 # relative to numpy-quant_amd/csrc) with the extra FLAGS and links tools/diag/libnqk_<name>.so
 # from them and the main build's other objects.  e.g.
-#   bash tools/diag_build.sh lnnt=nqk_fused.hip:-DNQK_LN_NT=1
+#   bash tools/diag_build.sh embst=nqk_gemm.hip:-DNQK_EMBED_DIAG=4
 set -e
 cd "$(dirname "$0")/../numpy-quant_amd/csrc"
 make -s -j8

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "numpy-quant_amd"))
 from numpy_quant import _lib  # noqa: E402
 from numpy_quant.device import DeviceArray  # noqa: E402
 
-if os.environ.get("GM_LIB"):  # a diagnostic build (tools/gemm_diag.sh)
+if os.environ.get("GM_LIB"):  # a diagnostic build (tools/diag_build.sh)
     _lib.LIB_PATH = os.environ["GM_LIB"]
 _lib.ensure_init()
 M = int(os.environ.get("GM_M", 256 * 197))
