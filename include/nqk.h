@@ -78,8 +78,7 @@ int nqk_event_create(void** event);
 int nqk_event_record(void* event);
 int nqk_event_elapsed(void* start, void* stop, float* ms);   /* waits for stop */
 int nqk_event_destroy(void* event);
-/* the current stream waits for the work an event recorded (cross-stream ordering of the fused
- * plan's batch parts: NQK_STREAM_LAG) */
+/* the current stream waits for the work an event recorded (cross-stream ordering) */
 int nqk_event_wait(void* event);
 /* Pinned (page-locked) host memory and the asynchronous upload from it (QModel.classify_stream:
  * batch k + 1 travels while batch k computes).  nqk_upload_async enqueues the copy on the

@@ -1684,132 +1684,6 @@ k_ln_quant_lds(const float* __restrict__ x, const float* __restrict__ g, const f
     if (row0 + rr < rows) *reinterpret_cast<v4i*>(out + (row0 + rr) * COLS + c * 16) = v;
   }
 }
-// Persistent form (round 5, NQK_LN_PERS): one-wave workgroups, LN_PERS_W per CU, each walking
-// row groups g, g + grid, ... with the next group's rows loaded by LDS-DMA into the second half
-// of a double-buffered image while the current group is reduced, quantized and stored (the
-// single-shot kernel's waves load, then compute, then store: in a grid that is one or a few
-// waves per slot those phases line up across the chip).  gamma / beta stay in registers (a
-// lane's columns are the same in every group).  Same arithmetic as k_ln_quant_lds.
-template <int NL, bool MQ>
-__global__ void __launch_bounds__(64)
-k_ln_quant_pers(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                int8_t* __restrict__ out, int64_t rows, float eps, double rs, double zp, double lo, double hi, LnQ mq) {
-  constexpr int LF = 96, LPR = NL * 2, NI = LF / 8, COLS = NL * LF, RW = 64 / LPR;
-  constexpr int CH = COLS / 4, RSI = COLS * 4, RSO = COLS + 16, WLDS = RW * RSI;
-  constexpr int NLD = RW * CH / 64, NST = RW * COLS / 16 / 64;
-  static_assert(RW * CH % 64 == 0 && RW * COLS % 1024 == 0 && RW * RSO <= WLDS, "k_ln_quant_pers: shape");
-  extern __shared__ __attribute__((aligned(16))) int8_t lds[];
-  const int lane = threadIdx.x;
-  const int64_t ngroups = (rows + RW - 1) / RW;
-  int64_t grp = blockIdx.x;
-  if (grp >= ngroups) return;
-  // rx0: an empty buffer (loads return 0, no memory access) for the pieces issued after the
-  // last group, so every iteration issues the same NLD pieces (uniform counted waits: the
-  // compiler's own wait for the previous stores' data registers is then vmcnt(NLD), not 0)
-  const rsrc_t rx = make_rsrc(x, (uint32_t)((uint64_t)rows * COLS * 4)), rx0 = make_rsrc(x, 0u);
-  auto issue = [&](int64_t gi, int8_t* img, rsrc_t rr) {
-#pragma unroll
-    for (int k = 0; k < NLD; ++k) {
-      const int P = k * 64 + lane, r = P / CH, c = ln_swz(NL, r, P - r * CH);
-      const int64_t gr = gi * RW + r < rows ? gi * RW + r : rows - 1;
-      buf_lds16(rr, img + k * 1024, (uint32_t)(gr * COLS + c * 4) * 4u, 0u);
-    }
-  };
-  const int r = lane / LPR, u = lane % LPR, leaf = u >> 1, gq = u & 1;
-  const int c0 = leaf * LF + 4 * gq;
-  v2f_t gl[NI], gh[NI], bl[NI], bh[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const float4 gg = *reinterpret_cast<const float4*>(g + c0 + 8 * i);
-    const float4 bb = *reinterpret_cast<const float4*>(b + c0 + 8 * i);
-    gl[i] = v2f_t{gg.x, gg.y}, gh[i] = v2f_t{gg.z, gg.w}, bl[i] = v2f_t{bb.x, bb.y}, bh[i] = v2f_t{bb.z, bb.w};
-  }
-  // the parameters are in registers before any LDS-DMA is counted (the loop's waits are exact)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(gl[i]), "+v"(gh[i]), "+v"(bl[i]), "+v"(bh[i]));
-  issue(grp, lds, rx);
-  for (int cur = 0; grp < ngroups; grp += gridDim.x, cur ^= 1) {
-    int8_t* const wl = lds + cur * WLDS;
-    const int64_t nxt = grp + gridDim.x;
-    // the other half held the previous group's staged output, read (lgkmcnt 0) before its stores;
-    // vmcnt(NLD): this group's pieces (and the previous group's stores, issued before the next
-    // pieces) are done, the next group's NLD pieces stay in flight
-    issue(nxt < ngroups ? nxt : grp, lds + (cur ^ 1) * WLDS, nxt < ngroups ? rx : rx0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-    __builtin_amdgcn_wave_barrier();
-    // the tree reads by inline asm, their lgkmcnt wait tied to the values: a compiler-visible LDS
-    // read is given an s_waitcnt vmcnt(0) for the LDS-DMA in flight (it cannot tell the halves
-    // apart), which would drain the next group's pieces
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    v4f_t tv[NI];
-    static_assert(NI == 12, "k_ln_quant_pers: 12 tree reads");
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const uint32_t a = (uint32_t)(uintptr_t)(lds_ptr_t)(wl + r * RSI + ln_swz(NL, r, leaf * (LF / 4) + 2 * i + gq) * 16);
-      asm volatile("ds_read_b128 %0, %1" : "=v"(tv[i]) : "v"(a));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]), "+v"(tv[4]), "+v"(tv[5]), "+v"(tv[6]),
-                   "+v"(tv[7]), "+v"(tv[8]), "+v"(tv[9]), "+v"(tv[10]), "+v"(tv[11])::"memory");
-    v2f_t xl[NI], xh[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) xl[i] = v2f_t{tv[i][0], tv[i][1]}, xh[i] = v2f_t{tv[i][2], tv[i][3]};
-    v2f_t al = xl[0], ah = xh[0];
-#pragma unroll
-    for (int i = 1; i < NI; ++i) al = al + xl[i], ah = ah + xh[i];
-    float acc = (al[0] + al[1]) + (ah[0] + ah[1]);
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) acc = acc + __shfl_xor(acc, m, 64);
-    const float nmean = -(acc / (float)COLS);
-    const v2f_t nm2 = v2f_t{nmean, nmean};
-#pragma unroll
-    for (int i = 0; i < NI; ++i) xl[i] = xl[i] + nm2, xh[i] = xh[i] + nm2;
-    al = xl[0] * xl[0], ah = xh[0] * xh[0];
-#pragma unroll
-    for (int i = 1; i < NI; ++i) al = al + xl[i] * xl[i], ah = ah + xh[i] * xh[i];
-    float v2 = (al[0] + al[1]) + (ah[0] + ah[1]);
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) v2 = v2 + __shfl_xor(v2, m, 64);
-    const float inv = 1.0f / __builtin_sqrtf(v2 / (float)COLS + eps);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tree reads done before the staging overwrites
-    __builtin_amdgcn_wave_barrier();
-    const v2f_t i2 = v2f_t{inv, inv};
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const v2f_t yl = ((xl[i] * i2) * gl[i]) + bl[i], yh = ((xh[i] * i2) * gh[i]) + bh[i];
-      const float y[4] = {yl[0], yl[1], yh[0], yh[1]};
-      uint32_t packed = 0;
-      if constexpr (MQ) {
-        packed = ln_quant4<true>(y, rs, mq);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float t = (float)((double)y[k] * rs);
-          const int q = (int)__builtin_rint(__builtin_fmin(__builtin_fmax(zp + (double)t, lo), hi));
-          packed |= ((uint32_t)(q & 0xff)) << (8 * k);
-        }
-      }
-      *reinterpret_cast<uint32_t*>(wl + r * RSO + c0 + 8 * i) = packed;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const int64_t row0 = grp * RW;
-    v4i sv[NST];
-#pragma unroll
-    for (int k = 0; k < NST; ++k) {
-      const int C = k * 64 + lane, rr = C / (COLS / 16), c = C - rr * (COLS / 16);
-      sv[k] = *reinterpret_cast<const v4i*>(wl + rr * RSO + c * 16);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // staging read before the next issue refills it
-#pragma unroll
-    for (int k = 0; k < NST; ++k) {
-      const int C = k * 64 + lane, rr = C / (COLS / 16), c = C - rr * (COLS / 16);
-      if (row0 + rr < rows) *reinterpret_cast<v4i*>(out + (row0 + rr) * COLS + c * 16) = sv[k];
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may land after the wave's LDS is released
-}
 constexpr int ln_lds_bytes(int nl, int wpb = 4) { return wpb * (64 / (2 * nl)) * (nl * 96 * 4); }
 
 // ------------------------------------------------------------------ Softmax + quantize
@@ -2205,29 +2079,10 @@ extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* bet
     // rows through LDS: linear 1 KiB loads / stores per wave (the LDS-DMA form addresses x by 32-bit
     // buffer offsets: larger inputs take the register-tree kernel)
     const bool dma_ok = rows * cols * 4 < (int64_t(1) << 31);
-    const char* pe = getenv("NQK_LN_PERS");
-    if (dma_ok && pe && atoi(pe) > 0 && mq && !getenv("NQK_LN_REG")) {
-      // persistent double-buffered form: NQK_LN_PERS waves per CU (1-wave workgroups, 24 KiB each)
-      const int64_t ngroups = (rows + 32 / p.nleaf - 1) / (32 / p.nleaf);
-      const int64_t w = std::min<int64_t>(ngroups, (int64_t)std::min(6, atoi(pe)) * num_cus());
-      const int lb = 2 * (32 / p.nleaf) * p.nleaf * 96 * 4;
-#define LNP(NLV)                                                                                                 \
-  hipLaunchKernelGGL((k_ln_quant_pers<NLV, true>), dim3((unsigned)w), dim3(64), lb, stream(), x, gamma, beta, out, \
-                     rows, eps, rs, (double)zp, lo, hi, lq)
-      switch (p.nleaf) {
-        case 8: LNP(8); break;
-        case 4: LNP(4); break;
-        default: LNP(2); break;
-      }
-#undef LNP
-      return launch_status("nqk_ln_quant(pers)");
-    }
     if (!getenv("NQK_LN_REG") && dma_ok) {
-      // WPB waves of 64 / (2 nleaf) rows per workgroup; NQK_LN_WPB = 1 / 2 / 4 (default: 4 for 8 leaves,
-      // 1 for fewer — ViT-Ti's 192-column rows +1.3 % whole-bench, ViT-Base's -0.5 %, within noise:
-      // profiles/r05_ln_variants.txt)
-      const char* we = getenv("NQK_LN_WPB");
-      const int wpb = we ? (atoi(we) == 1 ? 1 : atoi(we) == 2 ? 2 : 4) : (p.nleaf == 8 ? 4 : 1);
+      // WPB waves of 64 / (2 nleaf) rows per workgroup: 4 for 8 leaves, 1 for fewer (ViT-Ti's 192-column
+      // rows +1.3 % whole-bench, ViT-Base's -0.5 %, within noise: profiles/r05_ln_variants.txt)
+      const int wpb = p.nleaf == 8 ? 4 : 1;
       const int64_t rpw = wpb * 32 / p.nleaf;
       const unsigned gl = (unsigned)((rows + rpw - 1) / rpw);
 #define LNL2(NLV, W)                                                                                               \
@@ -2237,17 +2092,12 @@ extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* bet
   else                                                                                                             \
     hipLaunchKernelGGL((k_ln_quant_lds<NLV, false, W>), dim3(gl), dim3(64 * W), ln_lds_bytes(NLV, W), stream(), x, \
                        gamma, beta, out, rows, eps, scale, rs, (double)zp, lo, hi, lq)
-#define LNL(NLV)                \
-  if (wpb == 1) LNL2(NLV, 1);   \
-  else if (wpb == 2) LNL2(NLV, 2); \
-  else LNL2(NLV, 4)
       switch (p.nleaf) {
-        case 8: LNL(8); break;
-        case 4: LNL(4); break;
-        default: LNL(2); break;
+        case 8: LNL2(8, 4); break;
+        case 4: LNL2(4, 1); break;
+        default: LNL2(2, 1); break;
       }
 #undef LNL2
-#undef LNL
       return launch_status("nqk_ln_quant(lds)");
     }
     switch (p.nleaf) {

@@ -83,8 +83,6 @@ static int pg_num_cus() {
   return n;
 }
 
-static int pg_num_xcds() { return xcd_count(); }
-
 // Launches k_pg for one projection GEMM when it takes the case; returns the kernel id for
 // nqk_qgemm_last_kernel (4 k_pg, 6 k_pg with the GELU table) if launched, 0 if the caller
 // must use another kernel, < 0 on error.  bp: the nqk_pack_pg image.  (Round 4's k_pg2 —
@@ -175,7 +173,7 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   e.add1 = p->add1;
   e.mul2 = p->mul2;
   e.ldo = (int)N;
-  e.xcds = pg_num_xcds();
+  e.xcds = xcd_count();
   e.lut = glut ? p->gelu_lut : nullptr;
   e.lut_bytes = glut ? (uint32_t)((8 * p->lut_n + 15) & ~15) : 0u;
   e.gk = GLutK{p->lut_k[0], p->lut_k[1], p->lut_k[2], p->lut_k[3], p->lut_k[4]};
@@ -187,30 +185,14 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
     const float g_abs = (float)(GELU_ABS * ars) + 0x1p-100f;
     e.g_lim = (float)((0.5 - (double)g_abs) * (1.0 - 0x1p-22));
   }
-  // K = 192 (three k steps): NQK_PG_RB=1 keeps the weight panel resident (RB; measured no faster
-  // at the ViT-Ti shapes: QKV 23.4 vs 23.4 us, GELU table 34.6 vs 34.9, profiles/r05_tiny_rb_embed_ab.txt)
-  const char* rbv = getenv("NQK_PG_RB");
-  const bool rb = K == 192 && !b4 && epi != PG_RESID && rbv && atoi(rbv) != 0;
-  // K = 192, QKV / GELU, int8: 64-row tiles with NQK_PG_WM0=1 (WM = 0; measured slower: the 128-row
-  // form's time is linear in its tiles, a partial last pass costs nothing extra, and the 64-row
-  // tiles read B twice per output — QKV 22.8 vs 19.2 us, profiles/r05_pg_rows64_dropped.txt)
-  {
-    const char* w0 = getenv("NQK_PG_WM0");
-    if (K == 192 && wm == 1 && epi != PG_RESID && !b4 && !rb && w0 && atoi(w0) == 1) wm = 0;
-  }
-  const int bm = wm ? wm * PG_BM : PG_BM / 2;
+  const int bm = wm * PG_BM;
   const int tiles_n = (int)((N + PG_BN - 1) / PG_BN), tiles_m = (int)((M + bm - 1) / bm);
   const int nt = tiles_m * tiles_n;
-  // NQK_PG_WGPC=1: one workgroup per CU (the other half of the register file free for the other
-  // stream's kernels: A/B switch with NQK_STREAM_LAG)
-  const char* wgpc = getenv("NQK_PG_WGPC");
-  const int slots = (wm == 2 || (wgpc && atoi(wgpc) == 1) ? 1 : 2) * pg_num_cus();
-  const int kc = K == 3072 ? 2 : (K == 192 ? 1 : 0);
+  const int slots = (wm == 2 ? 1 : 2) * pg_num_cus();
   // a single-line table (lut_k[2] == 0: the L line is -inf) takes the epilogue without it
   const int epi_k = glut ? (p->lut_k[2] == 0.0f ? PG_GLUT1 : PG_GLUT) : epi;
   const bool s8 = epi == PG_QKV && p->bit_width == 8 && !b4 && !getenv("NQK_PG_NOS8");
-  const int key = pg_key(epi_k, K == 3072 ? 48 : (K == 192 ? 3 : 12), f32x, b4, s8, wm, rb);
-  (void)kc;
+  const int key = pg_key(epi_k, K == 3072 ? 48 : (K == 192 ? 3 : 12), f32x, b4, s8, wm);
   const PgArgs x{a, bp, (int)M, (int)N, (int)lda, tiles_n, nt, nt < slots ? nt : slots, &e};
   // (A tail split — the rows of the whole rounds in one launch, the last round's row panels
   // in a second launch with one workgroup per tile — measured slower: FFN-down 142 -> 176 us,

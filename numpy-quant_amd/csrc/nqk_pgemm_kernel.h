@@ -68,7 +68,7 @@ constexpr int PG_TR_ROW = 272;  // bytes per staged residual row (256 + 16: conf
 constexpr int NQK_PG_WM2_RD = 3;  // ring depth of the 256 x 256 form's non-residual instances (4 fits its LDS)
 // ring depth: 3 stages, or NQK_PG_WM2_RD for the 256 x 256 form where K is a multiple of 4 k steps
 constexpr int pg_rd(int epi, int wm, int nk) { return (wm == 2 && epi != PG_RESID && nk % 4 == 0) ? NQK_PG_WM2_RD : PG_RD; }
-constexpr int pg_stg(bool b4, int wm = 1) { return (wm ? PG_ASTG * wm : PG_ASTG / 2) + PG_BN * (b4 ? PG_BK / 2 : PG_BK); }
+constexpr int pg_stg(bool b4, int wm = 1) { return PG_ASTG * wm + PG_BN * (b4 ? PG_BK / 2 : PG_BK); }
 constexpr int pg_colp(bool b4, int wm = 1, int rd = PG_RD) { return rd * pg_stg(b4, wm); }
 constexpr int pg_lds_bytes(int epi, bool b4, int wm = 1, int nk = 12) {
   return pg_colp(b4, wm, pg_rd(epi, wm, nk)) + 4096 + (pg_is_glut(epi) ? 8 * (wm == 2 ? GLUT_MAX : GLUT_CAP1) : 0) +
@@ -346,32 +346,20 @@ constexpr float NQK_PG_QKC2 = 0x1.5p-22f;  // 5.25 2^-24 per |c2|
 // S8 (QKV with 8-bit outputs): v_cvt_pk_u8_f32 saturates to [0, 255] (tools/micro/cvtu8.hip:
 // every integral f32 in [-2^24, 2^24], profiles/r04_cvtu8.txt), which is then the clamp, so the
 // v_med3 before it goes.
-// RB (round 5, K = 192 = three k steps: ViT-Ti): the whole K of a tile fits the ring, so the
-// weight panel stays RESIDENT — tiles are numbered column-panel major, a workgroup reloads B only
-// when its next tile is in another panel, and streams only A (24 KiB -> 8 KiB of operand bytes
-// per tile: one third); the k loop runs without loads or barriers, the next tile's A is issued
-// right after it, under the epilogue.
-// WM = 0 (round 5, K = 192: ViT-Ti's QKV and FFN-up; opt-in NQK_PG_WM0=1): 64-row tiles — twice
-// the tiles, for a less partial last pass of the persistent grid (ViT-Ti B = 256: 2 364 tiles = 4.6
-// passes instead of 1 182 = 2.3); one A piece per wave per stage, the k step's 16 MFMAs (subtiles
-// 0..3) split 8 + 8 around the stage wait.  Measured slower (the 128-row form's time is linear in its
-// tiles; 64-row tiles read B twice per output), profiles/r05_pg_rows64_dropped.txt.
-template <int EPI, int NK, bool F32X, bool B4, bool S8 = false, int WM = 1, bool RB = false>
+template <int EPI, int NK, bool F32X, bool B4, bool S8 = false, int WM = 1>
 __global__ void __launch_bounds__(256 * (WM == 2 ? 2 : 1), WM == 2 ? 1 : 2)
 k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, int lda, int tiles_n, int ntiles,
      PgEpi e) {
-  constexpr int RD = RB ? PG_RD : pg_rd(EPI, WM, NK);  // ring stages
+  constexpr int RD = pg_rd(EPI, WM, NK);  // ring stages
   static_assert(NK % RD == 0 && (NK >= 2 * RD || NK == RD), "k_pg: NK a multiple of the ring depth");
   static_assert(RD == PG_RD || EPI != PG_RESID, "k_pg: the residual epilogue borrows ring slot 2 (3 stages)");
-  static_assert(WM == 0 || WM == 1 || WM == 2, "k_pg: a 64-row tile, or one or two 128-row halves per tile");
-  static_assert(WM != 0 || (!B4 && !RB && EPI != PG_RESID), "k_pg<WM = 0>: int8, QKV / GELU only");
+  static_assert(WM == 1 || WM == 2, "k_pg: one or two 128-row halves per tile");
   constexpr int WQ = WM == 2 ? 2 : 1;            // 4-wave groups per workgroup
-  constexpr int APW = WM == 0 ? 1 : 2;           // A LDS-DMA pieces per wave per stage
-  constexpr int MS = WM == 0 ? 4 : 8;            // 16-row subtiles of a wave
-  static_assert(!RB || (NK == PG_RD && !B4 && EPI != PG_RESID), "k_pg<RB>: K = 3 k steps, int8, not residual");
+  constexpr int APW = 2;                         // A LDS-DMA pieces per wave per stage
+  constexpr int MS = 8;                          // 16-row subtiles of a wave
   constexpr bool RESID = EPI == PG_RESID;
-  constexpr int BM = WM ? PG_BM * WM : 64;      // tile rows
-  constexpr int ASTG = WM ? PG_ASTG * WM : PG_ASTG / 2;  // A bytes of a stage
+  constexpr int BM = PG_BM * WM;                // tile rows
+  constexpr int ASTG = PG_ASTG * WM;            // A bytes of a stage
   constexpr int BROW = B4 ? PG_BK / 2 : PG_BK;  // bytes of one B row per k-step
   constexpr int NBP = (B4 ? 2 : 4) / WQ;        // B LDS-DMA pieces per wave per stage
   constexpr int STG = pg_stg(B4, WM), COLP = pg_colp(B4, WM, RD), LUTO = COLP + 4096;
@@ -404,15 +392,8 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   struct Src { uint32_t sa, sb; int r0, tn; };
   auto src_of = [&](int tile) __attribute__((always_inline)) {
     Src s;
-    int tm;
-    if constexpr (RB) {  // column-panel major: consecutive tiles share their weight panel
-      const int tms = ntiles / tiles_n;
-      s.tn = tile / tms;
-      tm = tile - s.tn * tms;
-    } else {
-      tm = tile / tiles_n;
-      s.tn = tile - tm * tiles_n;
-    }
+    const int tm = tile / tiles_n;
+    s.tn = tile - tm * tiles_n;
     // a ragged last tile row is computed as rows M - BM .. M - 1 (the rows it shares
     // with the tile above are written twice with the same values; host: out != resid)
     s.r0 = tm * BM < M - BM ? tm * BM : M - BM;
@@ -497,22 +478,6 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
         acc[4 * h + ii][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bb[j], aa[ii], ci[j], 0, 0, 0);
       else
         acc[4 * h + ii][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bb[j], aa[ii], acc[4 * h + ii][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      fn(Q);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-  };
-
-  // 8 MFMAs (subtiles 2 qi, 2 qi + 1) with fn(q) after MFMA q: the 64-row form (WM = 0)
-  auto quarter = [&](auto QI, auto FIRST, const v4i (&aa)[4], const v4i (&bb)[4], const v4i (&ci)[4], auto&& fn)
-      __attribute__((always_inline)) {
-    constexpr int qi = decltype(QI)::value;
-    sfor<0, 8>([&](auto Q) __attribute__((always_inline)) {
-      constexpr int q = decltype(Q)::value, ii = 2 * qi + (q >> 2), j = q & 3;
-      if constexpr (decltype(FIRST)::value)
-        acc[ii][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bb[j], aa[ii], ci[j], 0, 0, 0);
-      else
-        acc[ii][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bb[j], aa[ii], acc[ii][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       fn(Q);
       __builtin_amdgcn_sched_barrier(0);
@@ -821,84 +786,6 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   constexpr int EOPS = RESID ? 32 : MS;
   constexpr int PWA = PW;
   Src cur = src_of(tile_at(0));
-  if constexpr (RB) {
-    // VMEM operations per wave, in issue order: [B pieces when the panel changes], colp(next),
-    // the next tile's A pieces (3 k steps), then the epilogue's EOPS stores: waiting for all but
-    // EOPS waits for everything the next tile reads
-    if constexpr (pg_is_glut(EPI)) pg_dma16(pg_rsrc(e.lut, e.lut_bytes), lds + LUTO + wave * 1024, 16 * lane, 1024u * wave);
-    auto issue_b = [&](const Src& s) __attribute__((always_inline)) {
-#pragma unroll
-      for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-        for (int p = 2; p < PW; ++p) issue_piece(s, kt, kt, p);
-    };
-    auto issue_a = [&](const Src& s) __attribute__((always_inline)) {
-#pragma unroll
-      for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) issue_piece(s, kt, kt, p);
-    };
-    int ctn = cur.tn;
-    issue_b(cur);
-    issue_colp(cur.tn, 0);
-    issue_a(cur);
-    for (int it = 0; it < iters; ++it) {
-      // s_setprio 0 in the k loop, 1 in the epilogue: the epilogue's VALU ahead of the other
-      // workgroup's k loop on the SIMD (-2..-4 %, profiles/r03c_*)
-      __builtin_amdgcn_s_setprio(0);
-      const bool more = it + 1 < iters;
-      const Src nxt = src_of(tile_at(more ? it + 1 : it));
-      const int cs = it & 1;
-      if (it == 0) pg_vmcnt<0>();
-      else pg_vmcnt<EOPS>();
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      v4i cinit[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cinit[j] = pg_lds16(lds + COLP + cs * 2048 + (64 * wn + 16 * lg + 4 * j) * 4);
-      sfor<0, 4>([&](auto Q) __attribute__((always_inline)) {
-        rd_a(a_lo, ic<0>{}, ic<0>{}, Q);
-        rd_b(b0, ic<0>{}, Q);
-      });
-      pg_lgkm_tie8(a_lo, b0);
-      pg_lgkm_tie(cinit[0], cinit[1], cinit[2], cinit[3]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cinit[j] = -cinit[j];
-      sfor<0, NK>([&](auto KT) __attribute__((always_inline)) {
-        constexpr int kt = decltype(KT)::value;
-        v4i(&bc)[4] = (kt & 1) ? b1 : b0;
-        v4i(&bn)[4] = (kt & 1) ? b0 : b1;
-        if constexpr (kt > 0) pg_lgkm_tie8(a_lo, bc);
-        half(ic<0>{}, std::integral_constant<bool, kt == 0>{}, a_lo, bc, cinit, [&](auto Q) __attribute__((always_inline)) {
-          constexpr int q = decltype(Q)::value;
-          if constexpr (q < 4) rd_a(a_hi, ic<kt>{}, ic<4>{}, Q);
-        });
-        pg_lgkm_tie(a_hi[0], a_hi[1], a_hi[2], a_hi[3]);
-        half(ic<1>{}, std::integral_constant<bool, kt == 0>{}, a_hi, bc, cinit, [&](auto Q) __attribute__((always_inline)) {
-          constexpr int q = decltype(Q)::value;
-          if constexpr (kt + 1 < NK) {
-            if constexpr (q < 4) rd_a(a_lo, ic<kt + 1>{}, ic<0>{}, Q);
-            else if constexpr (q < 8) rd_b(bn, ic<kt + 1>{}, ic<q - 4>{});
-          }
-        });
-      });
-      // every wave is done reading this tile's A (and B, if the panel changes)
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      if (nxt.tn != ctn) {  // (wave-uniform; rare: a workgroup's tiles are mostly one panel)
-        issue_b(nxt);
-        ctn = nxt.tn;
-      }
-      issue_colp(nxt.tn, cs ^ 1);
-      issue_a(nxt);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      epilogue(cur, cs);
-      cur = nxt;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return;
-  }
   // PG_GLUT: the 4 KiB GELU table into LDS, 1 KiB per wave (waited for with stage 0)
   // (WM = 2: the 8 KiB of a table of up to GLUT_MAX entries, 1 KiB per wave as well)
   // (the descriptor's range is the table's own 8 * lut_n bytes, rounded up to 16: the pieces past it
@@ -943,34 +830,6 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
       v4i(&bn)[4] = (kt & 1) ? b0 : b1;
       v2u(&pc)[4] = (kt & 1) ? p1 : p0;
       v2u(&pn)[4] = (kt & 1) ? p0 : p1;
-      if constexpr (WM == 0) {
-        // 64-row form: this step's A fragments (subtiles 0..3) alternate between a_lo and a_hi;
-        // MFMAs of subtiles 0, 1 (the refill of the slot step kt - 1 read after MFMA 4), the wait
-        // for stage kt + 1, then subtiles 2, 3 with the next step's fragment reads between them
-        v4i(&ac)[4] = (kt & 1) ? a_hi : a_lo;
-        v4i(&an)[4] = (kt & 1) ? a_lo : a_hi;
-        if constexpr (kt > 0) pg_lgkm_tie8(ac, bc);
-        quarter(ic<0>{}, std::integral_constant<bool, kt == 0>{}, ac, bc, cinit, [&](auto Q) __attribute__((always_inline)) {
-          if constexpr (kt + RD - 1 < NK && kt + RD - 1 > PRE && decltype(Q)::value == 4) issue_stage(cur, kt + RD - 1, (kt + RD - 1) % RD);
-        });
-        if constexpr (kt == 1) issue_colp(nxt.tn, cs ^ 1);
-        if constexpr (kt + 1 < NK) {
-          constexpr int hi_s = (kt + RD - 1 < NK ? kt + RD - 1 : NK - 1);
-          constexpr int y = (hi_s >= kt + 2 ? (hi_s - kt - 1) * PWA : 0) + ((kt >= 1 && kt <= RD - 1) ? 1 : 0);
-          if (kt + 1 <= PRE && it > 0) pg_vmcnt<y + EOPS>();
-          else pg_vmcnt<y>();
-          if constexpr ((NQK_PG_DIAG & 8) == 0) __builtin_amdgcn_s_barrier();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        quarter(ic<1>{}, std::integral_constant<bool, kt == 0>{}, ac, bc, cinit, [&](auto Q) __attribute__((always_inline)) {
-          constexpr int q = decltype(Q)::value;
-          if constexpr (kt + 1 < NK) {
-            if constexpr (q < 4) rd_a(an, ic<(kt + 1) % RD>{}, ic<0>{}, Q);
-            else rd_b(bn, ic<(kt + 1) % RD>{}, ic<q - 4>{});
-          }
-        });
-        return;
-      }
       if constexpr (kt > 0) {  // this step's fragments (read in step kt - 1)
         if constexpr (B4) {
           pg_lgkm_tie_a4(a_lo, pc);
@@ -1056,16 +915,15 @@ bool pg_dispatch_tiny(int key, const PgArgs& x);
 bool pg_dispatch_i4(int key, const PgArgs& x);
 bool pg_dispatch_wm2(int key, const PgArgs& x);
 
-// launch keys: EPI * 16 + (K 3072: 2, K 192: 1, else 0) * 4 + F32X + 2 B4 + 256 S8 + 512 WM2 + 1024 RB + 2048 WM0
-constexpr int pg_key(int epi, int nk, bool f32x, bool b4, bool s8, int wm, bool rb = false) {
+// launch keys: EPI * 16 + (K 3072: 2, K 192: 1, else 0) * 4 + F32X + 2 B4 + 256 S8 + 512 WM2
+constexpr int pg_key(int epi, int nk, bool f32x, bool b4, bool s8, int wm) {
   return epi * 16 + (nk == 48 ? 2 : (nk == 3 ? 1 : 0)) * 4 + (f32x ? 1 : 0) + (b4 ? 2 : 0) + (s8 ? 256 : 0) +
-         (wm == 2 ? 512 : 0) + (rb ? 1024 : 0) + (wm == 0 ? 2048 : 0);
+         (wm == 2 ? 512 : 0);
 }
-#define NQK_PG_CASE_RB(E, NKV, X, B, S, W, R)                                                                  \
-  case pg_key(E, NKV, X, B, S, W, R):                                                                          \
-    hipLaunchKernelGGL((k_pg<E, NKV, X, B, S, W, R>), dim3(x.grid), dim3(W == 2 ? 512 : 256), pg_lds_bytes(E, B, W, NKV), stream(), \
+#define NQK_PG_CASE(E, NKV, X, B, S, W)                                                                        \
+  case pg_key(E, NKV, X, B, S, W):                                                                             \
+    hipLaunchKernelGGL((k_pg<E, NKV, X, B, S, W>), dim3(x.grid), dim3(W == 2 ? 512 : 256), pg_lds_bytes(E, B, W, NKV), stream(), \
                        x.a, x.bp, x.m, x.n, x.lda, x.tiles_n, x.ntiles, *static_cast<const PgEpi*>(x.epi));    \
     return true;
-#define NQK_PG_CASE(E, NKV, X, B, S, W) NQK_PG_CASE_RB(E, NKV, X, B, S, W, false)
 
 }  // namespace nqk

@@ -96,24 +96,6 @@ class Streams:
 _ONE_STREAM = Streams(False)
 
 
-def _stream_lag():
-    v = os.environ.get("NQK_STREAM_LAG", "")
-    return v if v in ("ln1", "qkv", "attn") else None
-
-
-_LAG_EVENTS = {}
-
-
-def _lag_event(i):
-    """The event part i records at its NQK_STREAM_LAG point (one per part, reused every layer:
-    part i + 1 waits for it right after part i's layer is issued)."""
-    if i not in _LAG_EVENTS:
-        e = ctypes.c_void_p()
-        _lib.call("nqk_event_create", ctypes.byref(e))
-        _LAG_EVENTS[i] = e
-    return _LAG_EVENTS[i]
-
-
 def embed_q_fits(images: int, hw: int, kout: int) -> bool:
     """Whether one nqk_embed_q call over `images` images of hw patches takes the shape: at most
     65535 row tiles of 128 patches, and (images x (hw + 1)) x kout < 2^31 (its 32-bit output
@@ -515,12 +497,7 @@ class FusedEmbed:
                           self.wt.vp, self.bias.vp, self.cls.vp, self.posv.vp, ov.vp, nb, c, h, w, m.kh, m.kw,
                           self.kout)
 
-            if os.environ.get("NQK_EMBED_WHOLE") and embed_q_fits(n, hw, self.kout):
-                # A/B variant (round 6): one whole-batch launch on stream 0; the next split step forks
-                streams.join()
-                part(0, 0, n)
-            else:
-                streams.halves(n, part)
+            streams.halves(n, part)
             if t0 is not None:
                 KM.TIMER.end("embed_sgemm", t0, (2 * n * hw * self.kk * self.kout,
                                                  n * c * h * w + 4 * (self.kk * self.kout + n * (hw + 1) * self.kout)),
@@ -786,7 +763,7 @@ class FusedLayer:
         if not self.attn_fused:
             streams.join()  # the three-launch attention runs whole-batch on stream 0
             streams = _ONE_STREAM
-        streams.halves(B, lambda s_idx, i0, nb: self._run_part(w, x.dev, w["x1"], x2, i0, nb, s_idx, streams.parts))
+        streams.halves(B, lambda s_idx, i0, nb: self._run_part(w, x.dev, w["x1"], x2, i0, nb))
         m.x_out.data = FTensor(x2)
 
     def _run_cls(self, ws, w, x, B, streams):
@@ -807,7 +784,7 @@ class FusedLayer:
             def rows(arr):
                 ncol = arr.shape[-1]
                 return arr.offset_view(i0 * ncol, (nb, ncol))
-            self._run_part(w, x.dev, None, None, i0, nb, s_idx, streams.parts, q_rows=1)
+            self._run_part(w, x.dev, None, None, i0, nb, q_rows=1)
             copy_strided(w["ctx"], c["ctx"], (nb, D), (T * D, 1), (D, 1), i0 * T * D, i0 * D)
             copy_strided(x.dev, c["x"], (nb, D), (T * D, 1), (D, 1), i0 * T * D, i0 * D)
             self._back(rows(c["x"]), rows(c["ctx"]), rows(c["x1"]), rows(c["ln2q"]), rows(c["h"]),
@@ -830,20 +807,11 @@ class FusedLayer:
         self._run_part(w, x.dev, w["x1"], x2, 0, B, front=False)
         return x2
 
-    def _run_part(self, w, xd, x1d, x2d, i0, nb, s_idx=0, parts=1, q_rows=0, front=True):
-        """Images [i0, i0 + nb) of the layer (row views of every buffer).  NQK_STREAM_LAG
-        (ln1 / qkv / attn): part s > 0 starts the layer only after part s - 1 has finished that
-        kernel of it, so the parts' kernels of different kinds run side by side (A/B switch).
+    def _run_part(self, w, xd, x1d, x2d, i0, nb, q_rows=0, front=True):
+        """Images [i0, i0 + nb) of the layer (row views of every buffer).
         q_rows > 0: LN1, QKV and the attention of the first q_rows query rows only (the cls_tail
         layer's front); front = False: the attention and everything after it, from q / k / v."""
         m, bw = self.m, self.bw
-        lag = _stream_lag() if parts > 1 else None
-        if lag and s_idx > 0:
-            _lib.call("nqk_event_wait", _lag_event(s_idx - 1))
-
-        def mark(point):
-            if lag == point and s_idx + 1 < parts:
-                _lib.call("nqk_event_record", _lag_event(s_idx))
         T, D = m.tokens, self.D
         H, Dh, F = m.heads, m.hdim, self.F
         Mrows = nb * T
@@ -863,7 +831,6 @@ class FusedLayer:
             # layer's FFN-down epilogue computed it)
             if not self.ln1_by_prev:
                 _ln_quant(x, self.g1, self.be1, lnq, Mrows, D, self.eps1, self.p_ln1, bw)
-            mark("ln1")
             # 2) QKV projection: dequant + bias + head split + quantize with each head consumer's params
             s_a = np.float32(self.p_ln1.scale)
             e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln1), group_cols=D, col=self.col_qkv.ptr,
@@ -873,7 +840,6 @@ class FusedLayer:
                           zp_out=[_zp(self.p_head[r]) for r in "qkv"],
                           out=[q.ptr, k.ptr, v.ptr], bias=self.bias_qkv.ptr)
             _gemm(EPI_QKV, lnq, self._b(e, "qkv", self.bt_qkv), 1, Mrows, 3 * D, D, D, D, None, 0, 0, e)
-            mark("qkv")
         pq, pk, pv_ = self.p_head["q"], self.p_head["k"], self.p_head["v"]
         if self.attn_fused:
             # 3-6) one kernel per (image, head): scores, softmax, P V, context quantize
@@ -891,7 +857,6 @@ class FusedLayer:
                 KM.TIMER.end("attention", t0, (2 * 2 * nb * H * qr * T * Dh, nb * H * Dh * (qr + 2 * T) + nb * qr * D))
         else:
             self._attention_unfused(w, nb, T, Tp, H, Dh, D)  # whole batch only (i0 == 0)
-        mark("attn")
         if q_rows:
             return
         x1, x2 = (rows(t.reshape((t.size // D, D)), D) for t in (x1d, x2d))

@@ -243,8 +243,8 @@ _F32 = ["epi", "big", "pg", "proj"]
 
 # every route at the smallest shapes that reach it (input 4: random data, small output scales)
 ROUTE_CASES = [
-    (C("qkv", 131, 192, 192, "small"), ["epi", "big", "big_pack", "pg", "pg64"]),
-    (C("qkv", 197 * 3, 576, 192, "small"), ["epi", "big", "big_pack", "pg", "pg64"]),
+    (C("qkv", 131, 192, 192, "small"), ["epi", "big", "big_pack", "pg"]),
+    (C("qkv", 197 * 3, 576, 192, "small"), ["epi", "big", "big_pack", "pg"]),
     # (k_proj takes whole images only, M % tokens == 0: it must decline the partial last image, proj_fb)
     (C("qkv", 300, 768, 768, "small"), ["epi", "big", "big_pack", "proj_fb", "pg", "pg_wm2"]),
     (C("qkv", 256 + 77, 2304, 768, "small"), ["big", "proj_fb", "pg", "pg_wm2"]),
@@ -257,7 +257,7 @@ ROUTE_CASES = [
     (C("resid", 256 + 77, 768, 3072, l1=True), ["big", "pg", "pg_wm2"]),
     (C("resid", 256, 768, 3072, l1=True), ["proj", "pg"]),
     (C("resid", 131, 3072, 192), ["big", "pg"]),
-    (C("gelu", 131, 768, 192), ["epi", "big", "big_pack", "pg", "pg64", "glut"]),
+    (C("gelu", 131, 768, 192), ["epi", "big", "big_pack", "pg", "glut"]),
     (C("gelu", 300, 3072, 768, "small"), ["big", "big_pack", "proj", "pg", "pg_wm2", "glut", "glut_wm2"]),
     (C("gelu", 197 * 3, 768, 768, "small"), ["epi", "pg", "glut"]),
     # s_out = 0.0008: the increasing branch alone needs > 1024 buckets of 0.885 s, so nqk_gelu_lut_build
@@ -297,7 +297,7 @@ for _z in (2, 3):  # K = 3072 with col_l1max = 42 K: 128 L + L zpa = 16 773 120 
                       (C("gelu", 131, 768, 3072, "extreme", zpa=_z, l1=True), ["big"])]
 
 # input 2: exact ties
-TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "pg", "pg64"]),
+TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "pg"]),
               (C("qkv", 197 * 2, 768, 768, "ties"), ["big", "pg", "pg_wm2", "proj"])]
 
 # the fused LayerNorm of k_qgemm_big at N = 192: bit widths, ln_zp at +-2^20 (magic-number quantize) and beyond (f64)

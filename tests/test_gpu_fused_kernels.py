@@ -44,18 +44,13 @@ def test_ln_quant(rows, cols, bw, zp, path, monkeypatch):
 
 
 @pytest.mark.parametrize("rows,cols", [(4109, 768), (40000, 192), (9001, 384)])
-@pytest.mark.parametrize("variant", ["NQK_LN_WPB=1", "NQK_LN_WPB=2", "NQK_LN_WPB=4", "NQK_LN_PERS=1", "NQK_LN_PERS=4",
-                                     "NQK_LN_PERS=6"])
-def test_ln_quant_workgroup_forms_match_oracle(rows, cols, variant, monkeypatch):
-    """Every launch form of the LDS LayerNorm (nqk_fused.hip: 1 / 2 / 4 row groups per workgroup;
-    the persistent double-buffered k_ln_quant_pers at 1 / 4 / 6 waves per CU, whose waves walk
-    many row groups with the next group's LDS-DMA in flight — 40 000 x 192 at one wave per CU is
-    ~10 groups per wave; ragged last groups) against the oracle, bit for bit."""
+def test_ln_quant_workgroup_forms_match_oracle(rows, cols, monkeypatch):
+    """The three launch forms of the LDS LayerNorm (nqk_fused.hip k_ln_quant_lds: 8 leaves with 4 row
+    groups per workgroup, 4 and 2 leaves with one), each over many row groups with a ragged last
+    one, against the oracle, bit for bit."""
     from numpy_quant import _lib
     from numpy_quant.device import DeviceArray
     monkeypatch.delenv("NQK_LN_REG", raising=False)
-    k, v = variant.split("=")
-    monkeypatch.setenv(k, v)
     rng = np.random.default_rng(rows + cols)
     x = (rng.standard_normal((rows, cols)) * 3 - 0.7).astype(np.float32)
     g = (1 + 0.05 * rng.standard_normal(cols)).astype(np.float32)

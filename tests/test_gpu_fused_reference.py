@@ -12,7 +12,7 @@ and just above 2^24, exact rounding ties, output zero points at +-2^20 and one b
 to 2^20 (the non-int32 zero-point algebra), bit widths 2 and 3, small output scales, and for
 attention the zero-point limits of include/nqk.h with flat, peaked and -86.5-straddling rows.
 Shapes are the smallest that reach each route's mechanisms (3-, 12-, 48-step k loops, ragged
-tiles against 64 / 128 / 256 rows, an image boundary inside a tile), not the workload's."""
+tiles against 128 / 256 rows, an image boundary inside a tile), not the workload's."""
 import ctypes
 
 import numpy as np
@@ -23,8 +23,8 @@ import _fused_cases as F
 pytestmark = pytest.mark.gpu
 
 _SWITCHES = ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID", "NQK_PROJ_RESID", "NQK_PROJ_GELU", "NQK_PG_WM",
-             "NQK_PG_WM0", "NQK_NO_GELU_FILTER", "NQK_NO_GLUT", "NQK_GLUT_NO1", "NQK_GLUT_NOWIDE", "NQK_NO_L1",
-             "NQK_PROJ_CUS", "NQK_LN_F64Q", "NQK_PG_RB", "NQK_PG_WGPC", "NQK_NO_BPACK", "NQK_NO_B4", "NQK_XCDS",
+             "NQK_NO_GELU_FILTER", "NQK_NO_GLUT", "NQK_GLUT_NO1", "NQK_GLUT_NOWIDE", "NQK_NO_L1",
+             "NQK_PROJ_CUS", "NQK_LN_F64Q", "NQK_NO_BPACK", "NQK_NO_B4", "NQK_XCDS",
              "NQK_PG_NOS8")
 _PG = {"NQK_NO_PROJ": "1", "NQK_PG_WM": "1"}
 _PROJ = {"NQK_PROJ_RESID": "1", "NQK_PROJ_GELU": "1"}
@@ -39,7 +39,6 @@ ROUTES = {
     "proj_fb": (1, _PROJ, "pack", None, False),              # offered to k_proj, which must decline
     "pg": (4, _PG, "pack", "pg", False),
     "pg_fb": (1, _PG, "pack", "pg", False),                  # offered to k_pg, which must decline
-    "pg64": (4, dict(_PG, NQK_PG_WM0="1"), "pack", "pg", False),
     "pg4": (4, _PG, "pack4", "pg4", False),
     "pg_wm2": (5, {"NQK_NO_PROJ": "1", "NQK_PG_WM": "2"}, "pack", "pg", False),
     "glut": (6, _PG, "pack", "pg", True),
