@@ -197,10 +197,18 @@ int nqk_qgemm_generic(const void* a, int a_dtype, const void* b, int b_dtype, in
  * reference BLAS's summation: K is cut into OpenBLAS level-3 blocks (GEMM_Q=448
  * rule), each block a k-ordered fmaf chain from 0, blocks added in order.  Used
  * by Conv (numpy_helper.py:73-92 x.dot(w)) and by float MatMul/Gemm of the
- * calibration forward (model.py:153-157, 122-131 via np.matmul). */
+ * calibration forward (model.py:153-157, 122-131 via np.matmul).
+ * The split of a remainder between Q and 2 Q follows the OpenBLAS driver that NumPy's call takes
+ * for M, N, K and `threads` OpenBLAS threads: the single-thread driver rounds the half up to a
+ * multiple of 16, the threaded one takes the ceiling half.  Products of at most 10^6
+ * multiply-adds per matrix take OpenBLAS's small-matrix kernels instead (no K blocking; dot
+ * products with 16 accumulators in the column tails).  `transb` != 0 says that B is
+ * the transposed view of a row-major [N][K] matrix (a Gemm's w.T: b_sk = 1, b_sn = its row
+ * stride), whose small-matrix kernels are others; above 10^6 the order is the same. */
 int nqk_sgemm(const float* a, const float* b, float* c, int64_t batch, int64_t M, int64_t N,
               int64_t K, int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn, int64_t ldc,
-              const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride, int64_t c_mat_stride);
+              const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride, int64_t c_mat_stride,
+              int64_t threads, int64_t transb);
 
 /* One-row float product y[N] = x[1][K] . B[K][N] where B's columns are contiguous
  * (bt[N][ldb], the layout of the Gemm's w.T view, model.py:122-131): NumPy's matmul hands

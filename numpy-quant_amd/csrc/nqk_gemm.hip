@@ -9,10 +9,12 @@
 //  * nqk_sgemm        — float32 GEMM that reproduces the reference BLAS bit for
 //                       bit: OpenBLAS (scipy-openblas 0.3.29, SkylakeX kernels, the
 //                       one NumPy 2.2.6 ships on both hosts) cuts K into level-3
-//                       blocks (GEMM_Q = 448; a remainder in (Q, 2Q) is halved),
+//                       blocks (GEMM_Q = 448; a remainder in (Q, 2Q) is halved, by
+//                       the rule of the driver taken: blas_kblocks, gemm_threaded),
 //                       each block a k-ordered fmaf chain from 0, blocks summed in
-//                       order.  Verified against np.matmul for K = 64 .. 3072
-//                       (tests/test_host.py::test_blas_order_matches_numpy_matmul).
+//                       order; at most 10^6 multiply-adds take the small-matrix
+//                       kernels' orders (k_sgemm_small).  Pinned against np.matmul
+//                       by tests/test_sgemm_ref_host.py and tests/test_host.py.
 //  * nqk_im2col       — numpy_helper.py:18-70 sliding windows, NCHW input.
 #include "nqk_common.h"
 
@@ -1122,23 +1124,126 @@ k_sgemv_n(const float* __restrict__ x, const float* __restrict__ b, float* __res
   y[j] = yv;
 }
 
+// The small-matrix regime of np.matmul (gemm_small_regime; identified against np.matmul,
+// oracle/openblas_order.py sgemm_small, pinned by tests/test_sgemm_ref_host.py).  One lane per
+// output, no K blocking:
+//  * B row-major (BLAS NN): a k-ordered fma chain, except in the last N % 16 columns when that tail
+//    is at most 8 and K >= 32.  Those are dot products: 16 fma accumulators, accumulator l over
+//    k = l mod 16, reduced by adjacent pairs ((a0 + a1) + (a2 + a3)) + ..; the tail is cut into
+//    groups of 8, 4, 2, 1 columns, and in the 2- and 1-column groups the rows past the last
+//    multiple of 4 reduce by halves instead (a_l + a_{l + 8}, then + 4, + 2, + 1);
+//  * B a transposed view (BLAS TN): every output such a dot product, by halves where both the
+//    row is past M's and the column past N's last multiple of 4, by adjacent pairs elsewhere.
+__global__ void __launch_bounds__(256)
+k_sgemm_small(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C, int64_t M, int64_t N,
+              int64_t K, int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn, int64_t ldc, BatchMap bm, int64_t a_ms,
+              int64_t b_ms, int64_t c_ms, int transb) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= M * N) return;
+  const int64_t bz = blockIdx.z, i = e / N, j = e - i * N;
+  const float* a = A + map_a(bm, bz) * a_ms + i * a_sm;
+  const float* b = B + map_b(bm, bz) * b_ms + j * b_sn;
+  float* c = C + bz * c_ms + i * ldc + j;
+  int mode = 0;  // 0 chain, 1 dot by adjacent pairs, 2 dot by halves
+  if (transb) {
+    mode = (i >= (M & ~(int64_t)3) && j >= (N & ~(int64_t)3)) ? 2 : 1;
+  } else {
+    const int64_t mm = N & 15;
+    if (mm > 0 && mm <= 8 && K >= 32 && j >= N - mm) {
+      int64_t t = j - (N - mm), g = 8;
+      for (; g >= 1; g >>= 1)
+        if (mm & g) {
+          if (t < g) break;
+          t -= g;
+        }
+      mode = (g <= 2 && i >= (M & ~(int64_t)3)) ? 2 : 1;
+    }
+  }
+  if (mode == 0) {
+    float acc = 0.0f;
+    for (int64_t k = 0; k < K; ++k) acc = __builtin_fmaf(a[k * a_sk], b[k * b_sk], acc);
+    *c = acc;
+    return;
+  }
+  float acc[16];
+#pragma unroll
+  for (int l = 0; l < 16; ++l) acc[l] = 0.0f;
+  const int64_t k16 = K & ~(int64_t)15;
+  for (int64_t k0 = 0; k0 < k16; k0 += 16)
+#pragma unroll
+    for (int l = 0; l < 16; ++l) acc[l] = __builtin_fmaf(a[(k0 + l) * a_sk], b[(k0 + l) * b_sk], acc[l]);
+#pragma unroll
+  for (int l = 0; l < 16; ++l)
+    if (k16 + l < K) acc[l] = __builtin_fmaf(a[(k16 + l) * a_sk], b[(k16 + l) * b_sk], acc[l]);
+  if (mode == 1) {
+#pragma unroll
+    for (int w = 1; w < 16; w *= 2)
+#pragma unroll
+      for (int l = 0; l < 16; l += 2 * w) acc[l] = acc[l] + acc[l + w];
+  } else {
+#pragma unroll
+    for (int w = 8; w >= 1; w /= 2)
+#pragma unroll
+      for (int l = 0; l < w; ++l) acc[l] = acc[l] + acc[l + w];
+  }
+  *c = acc[0];
+}
+
 }  // namespace
 
-// OpenBLAS level-3 K blocking (driver/level3/level3.c): GEMM_Q = 448 for SkylakeX sgemm
-// (identified against np.matmul: 384 agrees only while K <= 768)
-static int blas_kblocks(int64_t K, KBlocks* kb) {
-  const int64_t Q = 448, U = 2;
+// OpenBLAS level-3 K blocking, GEMM_Q = 448 for SkylakeX sgemm: a remainder of 2 Q or more takes
+// Q; one between Q and 2 Q is split, and the two drivers split it differently (identified against
+// np.matmul, tests/test_sgemm_ref_host.py):
+//  * the single-thread driver (driver/level3/level3.c) takes half of it rounded up to a multiple
+//    of GEMM_UNROLL_M = 16: ((m / 2 + 15) / 16) * 16;
+//  * the threaded driver (level3_thread.c) takes its ceiling half: (m + 1) / 2.
+// They agree where m is even and m / 2 a multiple of 16: K = 768, 1536 and 3072 (the ViT's) block
+// alike under both, 384 + 384, 448 448 320 320 and 5 x 448 + 416 + 416.
+static int blas_kblocks(int64_t K, KBlocks* kb, bool threaded) {
+  const int64_t Q = 448, U = 16;
   int64_t ls = 0;
   kb->n = 0;
   while (ls < K) {
     int64_t min_l = K - ls;
     if (min_l >= 2 * Q) min_l = Q;
-    else if (min_l > Q) min_l = ((min_l / 2 + U - 1) / U) * U;
+    else if (min_l > Q) min_l = threaded ? (min_l + 1) / 2 : ((min_l / 2 + U - 1) / U) * U;
     ls += min_l;
     if (kb->n >= 24) return -1;
     kb->end[kb->n++] = ls;
   }
   return 0;
+}
+
+// Which of the two drivers OpenBLAS 0.3.29 takes for a row-major M x N x K product (BLAS m = N,
+// n = M) with `threads` threads: interface/gemm.c allows M N K / (65536 * 4) threads, at most
+// `threads`; with one it calls the single-thread driver; else level3_thread.c splits m over
+// nthreads_m (halved until m >= 16 nthreads_m; 1 below m = 32) and n over nthreads_n, and takes
+// the single-thread driver when that leaves one part.
+static bool gemm_threaded(int64_t M, int64_t N, int64_t K, int64_t threads) {
+  const int64_t S = 16;  // SWITCH_RATIO
+  int64_t avail = (int64_t)((double)M * (double)N * (double)K / 262144.0);
+  if (avail < 1) avail = 1;
+  const int64_t nth = threads < avail ? threads : avail;
+  if (nth <= 1) return false;
+  const int64_t m = N, n = M;
+  int64_t nm = 1, nn = 1;
+  if (m >= 2 * S) {
+    nm = nth;
+    while (m < nm * S) nm /= 2;
+  }
+  if (n >= S * nm) {
+    nn = (n + S * nm - 1) / (S * nm);
+    if (nm * nn > nth) nn = nth / nm;
+  }
+  return nm * nn > 1;
+}
+
+// OpenBLAS's small-matrix kernels (interface/gemm.c, SMALL_MATRIX_OPT; SkylakeX permit): products
+// of at most 100^3 multiply-adds; with B a transposed view (BLAS TN) only for M N <= 1200 and
+// K >= 32.  No K blocking there.
+static bool gemm_small_regime(int64_t M, int64_t N, int64_t K, bool transb) {
+  if ((double)M * (double)N * (double)K > 1000000.0) return false;
+  return !transb || (M * N <= 1200 && K >= 32);
 }
 
 }  // namespace nqk
@@ -1152,6 +1257,13 @@ static bool kblocks_al16(int64_t K, const KBlocks& kb) {
   if (K % 16) return false;
   for (int i = 0; i < kb.n; ++i)
     if (kb.end[i] % 16) return false;
+  return true;
+}
+
+static bool kblocks_equal(const KBlocks& x, const KBlocks& y) {
+  if (x.n != y.n) return false;
+  for (int i = 0; i < x.n; ++i)
+    if (x.end[i] != y.end[i]) return false;
   return true;
 }
 
@@ -1190,15 +1302,25 @@ extern "C" int nqk_qgemm_generic(const void* a, int a_dtype, const void* b, int 
 
 extern "C" int nqk_sgemm(const float* a, const float* b, float* c, int64_t batch, int64_t M, int64_t N, int64_t K,
                          int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn, int64_t ldc, const int64_t* bmap,
-                         int64_t a_mat_stride, int64_t b_mat_stride, int64_t c_mat_stride) {
+                         int64_t a_mat_stride, int64_t b_mat_stride, int64_t c_mat_stride, int64_t threads,
+                         int64_t transb) {
   if (batch <= 0 || M <= 0 || N <= 0) return 0;
   if (batch > 65535 || (M + 63) / 64 > 65535) return fail("nqk_sgemm: grid too large");
+  if (threads < 1 || threads > 1024) return fail("nqk_sgemm: 1 <= threads <= 1024 expected");
+  BatchMap m = batch_map(bmap);
+  if (K > 0 && gemm_small_regime(M, N, K, transb != 0)) {
+    hipLaunchKernelGGL(k_sgemm_small, dim3((unsigned)((M * N + 255) / 256), 1, (unsigned)batch), dim3(256), 0, stream(), a,
+                       b, c, M, N, K, a_sm, a_sk, b_sk, b_sn, ldc, m, a_mat_stride, b_mat_stride, c_mat_stride,
+                       transb != 0 ? 1 : 0);
+    return launch_status("nqk_sgemm(small)");
+  }
   KBlocks kb;
   if (K <= 0) { kb.n = 0; kb.end[0] = -1; }
-  else if (blas_kblocks(K, &kb)) return fail("nqk_sgemm: K too large for the BLAS blocking table");
-  BatchMap m = batch_map(bmap);
+  else if (blas_kblocks(K, &kb, gemm_threaded(M, N, K, threads))) return fail("nqk_sgemm: K too large for the BLAS blocking table");
+  bool ends_even = true;  // the threaded driver's ceiling half can be odd inside an even K
+  for (int i = 0; i < kb.n; ++i) ends_even = ends_even && (kb.end[i] & 1) == 0;
   // MFMA path: same numerics (k-ordered fmaf chains), needs even K-block ends
-  if ((K & 1) == 0 && K > 0 && M * N >= 128 * 128 && !getenv("NQK_SGEMM_VALU")) {
+  if (ends_even && K > 0 && M * N >= 128 * 128 && !getenv("NQK_SGEMM_VALU")) {
     dim3 g2((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128), (unsigned)batch);
     if ((M + 127) / 128 > 65535) return fail("nqk_sgemm: grid too large");
     const bool vec = a_sk == 1 && b_sn == 1 && (N % 4) == 0 && (a_sm % 4) == 0 && (b_sk % 4) == 0 &&
@@ -1227,8 +1349,10 @@ extern "C" int nqk_sgemm_embed(const float* cols, const float* w, const float* b
   if (M <= 0 || N <= 0) return 0;
   if ((K & 1) || K <= 0) return fail("nqk_sgemm_embed: K must be even (MFMA k pairs)");
   if ((M + 127) / 128 > 65535) return fail("nqk_sgemm_embed: grid too large");
-  KBlocks kb;
-  if (blas_kblocks(K, &kb)) return fail("nqk_sgemm_embed: K too large for the BLAS blocking table");
+  KBlocks kb, kb1;
+  if (blas_kblocks(K, &kb, true) || blas_kblocks(K, &kb1, false))
+    return fail("nqk_sgemm_embed: K too large for the BLAS blocking table");
+  if (!kblocks_equal(kb, kb1)) return fail("nqk_sgemm_embed: a K that both OpenBLAS drivers block alike expected");
   const BatchMap m = batch_map(nullptr);
   dim3 g2((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128), 1);
   const bool vec = (N % 4) == 0 && ((((uintptr_t)cols) | ((uintptr_t)w)) & 15) == 0 && !getenv("NQK_SGEMM_SCALAR");
@@ -1269,7 +1393,7 @@ extern "C" int nqk_embed_q(const int8_t* q, float scale, int64_t zp, const float
   if ((M + 127) / 128 > 65535) return fail("nqk_embed_q: grid too large");
   if ((double)(M + images) * (double)N >= 2147483647.0) return fail("nqk_embed_q: output too large");
   KBlocks kb;
-  if (blas_kblocks(K, &kb) || !kblocks_al16(K, kb)) return fail("nqk_embed_q: K blocking");
+  if (blas_kblocks(K, &kb, true) || !kblocks_al16(K, kb)) return fail("nqk_embed_q: K blocking");  // 384 + 384, either driver
   const float zpf = (float)zp;
   // (a 3-stage LDS ring with the next k-tile's fragments read under the MFMAs measured 1.5 %
   // slower: 634 vs 625 us, profiles/r04_embed_ring_dropped.txt)

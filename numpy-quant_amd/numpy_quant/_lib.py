@@ -91,7 +91,7 @@ SIGNATURES = {
     "nqk_relu_q": [_p, _i, _p, _i, _l, _l],
     "nqk_qgemm_i8": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
     "nqk_qgemm_generic": [_p, _i, _p, _i, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
-    "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
+    "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l, _l, _l],
     "nqk_sgemv_t": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_sgemv_small": [_p, _p, _p, _l, _l, _l],
     "nqk_sgemv_n": [_p, _p, _p, _l, _l, _l, _l],

@@ -335,11 +335,51 @@ def weight_bt(b: DeviceArray):
 
 # ----------------------------------------------------------------------------- float GEMM
 def sgemm(a: DeviceArray, a_sm, a_sk, b: DeviceArray, b_sk, b_sn, M, N, K, batch=1, bmap=None,
-          a_ms=0, b_ms=0) -> DeviceArray:
+          a_ms=0, b_ms=0, transb=False) -> DeviceArray:
+    """C = A[M, K] . B[K, N] per matrix in np.matmul's order for OpenBLAS at openblas_threads()
+    threads (nqk_sgemm).  `transb`: B is, in the reference, the transposed view of a row-major
+    [N, K] matrix (a Gemm's w.T, a Transpose node's output); it selects the small-matrix kernels'
+    order and says nothing about the strides given here."""
     c = DeviceArray((batch, M, N) if batch > 1 else (M, N), np.float32)
     _lib.call("nqk_sgemm", a.vp, b.vp, c.vp, batch, M, N, K, a_sm, a_sk, b_sk, b_sn, N,
-              _lib.i64arr(bmap) if bmap is not None else None, a_ms, b_ms, M * N)
+              _lib.i64arr(bmap) if bmap is not None else None, a_ms, b_ms, M * N, openblas_threads(),
+              1 if transb else 0)
     return c
+
+
+def blas_kblocks(K: int, threaded: bool) -> list:
+    """OpenBLAS's level-3 K blocks (GEMM_Q = 448) under its threaded or its single-thread driver
+    (nqk_gemm.hip blas_kblocks)."""
+    out, ls = [], 0
+    while ls < K:
+        m = K - ls
+        if m >= 896:
+            m = 448
+        elif m > 448:
+            m = (m + 1) // 2 if threaded else ((m // 2 + 15) // 16) * 16
+        out.append(m)
+        ls += m
+    return out
+
+
+def gemm_small_regime(M: int, N: int, K: int, transb: bool = False) -> bool:
+    """Whether np.matmul of A[M, K] @ B[K, N] (M, N >= 2) runs OpenBLAS's small-matrix kernels
+    (SkylakeX permit: at most 100^3 multiply-adds; with B a transposed view only for M N <= 1200
+    and K >= 32) instead of the level-3 drivers.  nqk_gemm.hip gemm_small_regime is the same rule."""
+    if M * N * K > 1_000_000:
+        return False
+    return (not transb) or (M * N <= 1200 and K >= 32)
+
+
+def gemm_restated(M: int, N: int, K: int, transb: bool = False) -> bool:
+    """Whether A[M, K] @ B[K, N] with both operands contiguous (transb: B the transposed view of a
+    contiguous [N, K]) is computed in np.matmul's exact order (tests/test_sgemm_ref_host.py pins
+    the restatement, tests/_sgemm_ref.py, to np.matmul): both level-3 drivers' K blocks, and the
+    small-matrix kernels of both forms, every row and column class — every shape with M, N >= 2.
+    One-row and one-column products are the level-2 routines': one_row_restated.  Not covered by
+    this predicate (open regime): an A that is a transposed view in the reference (Gemm's
+    transA, a Transpose node feeding a MatMul's left operand) in the small regime."""
+    return M >= 2 and N >= 2 and K >= 1
 
 
 # OpenBLAS thread count of the NumPy whose GEMV order is reproduced (its column split
@@ -406,8 +446,9 @@ def sgemv_t(x: DeviceArray, bt: DeviceArray) -> DeviceArray:
     return y
 
 
-def matmul_f32(a: DeviceArray, b: DeviceArray) -> DeviceArray:
-    """np.matmul for float32 (batched, broadcast), BLAS summation order."""
+def matmul_f32(a: DeviceArray, b: DeviceArray, transb: bool = False) -> DeviceArray:
+    """np.matmul for float32 (batched, broadcast), BLAS summation order.  `transb` as sgemm's
+    (b is the materialised [.., K, N] either way)."""
     M, K = a.shape[-2:]
     K2, N = b.shape[-2:]
     if K != K2:
@@ -420,7 +461,7 @@ def matmul_f32(a: DeviceArray, b: DeviceArray) -> DeviceArray:
         b = materialize_broadcast(b, out_batch + (K, N))
         _, bmap = batch_map(out_batch, out_batch)
     nb = int(math.prod(out_batch))
-    c = sgemm(a, K, 1, b, N, 1, M, N, K, batch=nb, bmap=bmap, a_ms=M * K, b_ms=K * N)
+    c = sgemm(a, K, 1, b, N, 1, M, N, K, batch=nb, bmap=bmap, a_ms=M * K, b_ms=K * N, transb=transb)
     return c.reshape(out_batch + (M, N))
 
 

@@ -132,7 +132,15 @@ def _gemm(inputs, attrs):
                 return [FTensor(K.sgemv_small(x.dev, w.dev)) + b]
             if K.gemv_t_applies(1, n, k):
                 return [FTensor(K.sgemv_t(x.dev, w.dev)) + b]
-        w = w.T
+        if (isinstance(x, FTensor) and isinstance(w, FTensor) and x.dev.ndim == 2 and w.dev.ndim == 2
+                and not x.tview and not w.tview and w.dev.shape[0] >= 2
+                and K.gemm_small_regime(x.dev.shape[0], w.dev.shape[0], w.dev.shape[1], True)):
+            # the small-matrix kernels of the transposed form read w[N, K] as it lies
+            m, (n, k) = x.dev.shape[0], w.dev.shape
+            if x.dev.shape[1] != k:
+                raise ValueError(f"matmul: mismatch in core dimension ({x.dev.shape[1]} vs {k})")
+            return [FTensor(K.sgemm(x.dev, k, 1, w.dev, 1, k, m, n, k, transb=True)) + b]
+        w = w.T  # .tview: the matmul below takes the transposed form's order
     return [x.matmul(w) + b]
 
 

@@ -438,6 +438,10 @@ class FusedEmbed:
         self.posv = deq(m.pos).dev
         if self.kk % 2 or self.bias.size != self.kout or self.cls.size != self.kout:
             raise NoMatch("embedding dimensions")
+        if KM.blas_kblocks(self.kk, True) != KM.blas_kblocks(self.kk, False):
+            # the K blocks depend on the OpenBLAS driver, which depends on the batch: nqk_sgemm's to decide
+            raise NoMatch("embedding K blocks differ between the OpenBLAS drivers")
+        self.W = W
         self._cols = None
         # nqk_embed_q (no im2col matrix): 3-channel 16 x 16 patches, N % 64 == 0; the
         # weights as [N][K] in (ki, kj, ci) order, each 16-block of k permuted to the kernel's
@@ -469,6 +473,19 @@ class FusedEmbed:
         eshape = np.asarray(m.expand.inputs[1].data.data).reshape(-1)
         if eshape.size != 3 or int(eshape[0]) != n:
             raise ValueError(f"class-token Expand shape {eshape} does not match the batch {n}")
+        if KM.gemm_small_regime(n * hw, self.kout, self.kk):
+            # np.matmul takes OpenBLAS's small-matrix kernels for this Conv (no K blocking, dot-product
+            # column tails): the embedding kernels keep the level-3 order, so the node loop's own
+            # operators run instead (fconv2d -> nqk_sgemm decides the order)
+            from .tensor import fconv2d, concat
+            streams.join()
+            x = qmodel._dequant_input(m.x) if isinstance(xd, QTensor) else xd
+            y = fconv2d(x, FTensor(self.W), FTensor(self.bias), (0, 0, 0, 0), (m.kh, m.kw))
+            y = FTensor(y.dev.reshape((n, self.kout, hw))).transpose([0, 2, 1])
+            cls = FTensor(self.cls).expand(m.expand.inputs[1].data)
+            m.add.outputs[0].data = concat([cls, y], 1) + FTensor(self.posv)
+            m.conv_out.data = FusedAway(m.conv_out.name)
+            return
         out = DeviceArray((n, hw + 1, self.kout), np.float32)
         # (fused_in: the zero point within nqk_patchify_dequant's / nqk_embed_q's 2^20;
         # nqk_embed_q, per call (one per stream part): at most 65535 row tiles of 128 patches and

@@ -105,6 +105,11 @@ def _reshape_target(cur_shape, target) -> tuple[int, ...]:
 class FTensor:
     """float32 tensor in HBM (tensor.py:119-224)."""
 
+    # True where the reference holds this value as a transposed view whose second-to-last axis has
+    # unit stride (a Transpose node's / .T's output; here it is materialised): as the right operand
+    # of a matmul NumPy passes it to BLAS as a transposed matrix (kernels.sgemm transb)
+    tview = False
+
     def __init__(self, data: Union[np.ndarray, DeviceArray]):
         if isinstance(data, DeviceArray):
             if data.dtype != np.float32:
@@ -128,7 +133,7 @@ class FTensor:
 
     @property
     def T(self):
-        return FTensor(permute(self.dev, list(range(self.dev.ndim))[::-1]))
+        return self.transpose()
 
     def copy(self):
         return FTensor(self.dev.copy())
@@ -143,7 +148,14 @@ class FTensor:
         perm = axes[0] if len(axes) == 1 and not isinstance(axes[0], int) else axes
         if not perm:
             perm = list(range(self.dev.ndim))[::-1]
-        return FTensor(permute(self.dev, list(perm)))
+        out = FTensor(permute(self.dev, list(perm)))
+        nd = self.dev.ndim
+        p = [int(q) % nd for q in perm] if nd else []
+        if self.tview:  # a view of a view: only the identity keeps it (a 2-D .T.T is row-major again)
+            out.tview = p == list(range(nd))
+        else:  # the source's contiguous axis becomes the right operand's K axis
+            out.tview = nd >= 2 and p[-2] == nd - 1
+        return out
 
     def __neg__(self):
         return FTensor(K.unary(_lib.NEG, self.dev))
@@ -167,7 +179,7 @@ class FTensor:
         return FTensor(slice_dev(self.dev, ind))
 
     def matmul(self, other: "FTensor"):
-        return FTensor(K.matmul_f32(self.dev, other.dev))
+        return FTensor(K.matmul_f32(self.dev, other.dev, transb=other.tview))
 
     def div(self, other: "FTensor"):
         return FTensor(K.binary(_lib.DIV, self.dev, other.dev))

@@ -398,3 +398,88 @@ def sgemv_n(b: np.ndarray, x: np.ndarray, threads: int | None = None) -> np.ndar
         if m3:
             y[r1 - m3:r1] = _chain_n(x, b[:, r1 - m3:r1], 0, K)
     return y
+
+
+# ----------------------------------------------------------------------------- small-matrix GEMM
+# OpenBLAS 0.3.29's small-matrix sgemm kernels for SkylakeX (interface/gemm.c SMALL_MATRIX_OPT,
+# kernel/x86_64/sgemm_small_kernel_*_skylakex.c), which np.matmul reaches for products of at most
+# 100^3 multiply-adds; identified against np.matmul and pinned by tests/test_sgemm_ref_host.py.
+# For a row-major A[M, K] @ B[K, N] (BLAS sees C^T = B^T A^T, so its m is N and its n is M):
+#  * no K blocking; the result is stored as it is (beta = 0), so a sum that is -0 stays -0;
+#  * B row-major (NN): an output is a k-ordered fma chain, lane j % 16 of a 16-column group, the
+#    last group masked — except that a last group of at most 8 columns, when K >= 32, is computed
+#    as dot products: 16 fma accumulators, accumulator l over k = l mod 16 (a masked last step),
+#    reduced by adjacent pairs ((a0 + a1) + (a2 + a3)) + ...  The group is cut into pieces of
+#    8, 4, 2 and 1 columns; in the 2- and 1-column pieces, rows past the last multiple of 4 reduce
+#    by halves instead: a_l + a_{l+8}, then + 4, + 2, + 1;
+#  * B the transposed view of a row-major [N, K] (TN; taken only for M N <= 1200 and K >= 32):
+#    every output such a dot product, reduced by halves where the row is past M's and the column
+#    past N's last multiple of 4, by adjacent pairs elsewhere.
+def fma32(a, b, c) -> np.ndarray:
+    """Correctly rounded float32 fma, vectorised: the product of two f32 is exact in f64; the sum
+    with c by an error-free TwoSum; an inexact f64 sum is forced to odd before the one rounding to
+    f32 (53 >= 2 * 24 + 2 bits, also for subnormal f32 results).  Infinities and NaN follow the
+    f64 arithmetic (inf - inf, 0 * inf -> NaN; overflow -> inf at the cast)."""
+    a = np.asarray(a, np.float32).astype(np.float64)
+    b = np.asarray(b, np.float32).astype(np.float64)
+    c = np.asarray(c, np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        p = a * b
+        s = np.asarray(p + c)
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def fma_chain(a: np.ndarray, b: np.ndarray, k0: int = 0, k1: int | None = None) -> np.ndarray:
+    """[M, N] of k-ordered fma chains from +0 over k0 <= k < k1 of a[M, K], b[K, N]."""
+    k1 = a.shape[1] if k1 is None else k1
+    c = np.zeros((a.shape[0], b.shape[1]), np.float32)
+    for k in range(k0, k1):
+        c = fma32(a[:, k:k + 1], b[k:k + 1, :], c)
+    return c
+
+
+def dot16(a: np.ndarray, b: np.ndarray, halves: bool) -> np.ndarray:
+    """[M, N] of 16-accumulator dot products of a[M, K], b[K, N]."""
+    M, K = a.shape
+    N = b.shape[1]
+    acc = np.zeros((M, N, 16), np.float32)
+    bt = np.ascontiguousarray(b.T)
+    for k0 in range(0, K, 16):
+        n = min(16, K - k0)
+        acc[:, :, :n] = fma32(a[:, None, k0:k0 + n], bt[None, :, k0:k0 + n], acc[:, :, :n])
+    with np.errstate(all="ignore"):
+        while acc.shape[2] > 1:
+            h = acc.shape[2] // 2
+            acc = acc[:, :, :h] + acc[:, :, h:] if halves else acc[:, :, 0::2] + acc[:, :, 1::2]
+    return acc[:, :, 0]
+
+
+def sgemm_small(a: np.ndarray, b: np.ndarray, transb: bool = False) -> np.ndarray:
+    """np.matmul(a[M, K], b[K, N]) in the small-matrix kernels' order (M, N >= 2); `transb`: b is,
+    for NumPy, the transposed view of a row-major [N, K] matrix."""
+    a, b = _f(a), _f(b)
+    M, K = a.shape
+    N = b.shape[1]
+    m4, n4 = M & ~3, N & ~3
+    if transb:
+        out = dot16(a, b, False)
+        if m4 < M and n4 < N:
+            out[m4:, n4:] = dot16(a[m4:], b[:, n4:], True)
+        return out
+    out = fma_chain(a, b)
+    mm = N % 16
+    if 0 < mm <= 8 and K >= 32:
+        j = N - mm
+        for g in (8, 4, 2, 1):
+            if mm & g:
+                r = M if g >= 4 else m4
+                if r:
+                    out[:r, j:j + g] = dot16(a[:r], b[:, j:j + g], False)
+                if r < M:
+                    out[r:, j:j + g] = dot16(a[r:], b[:, j:j + g], True)
+                j += g
+    return out

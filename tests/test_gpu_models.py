@@ -98,9 +98,11 @@ def tainted_values(model):
     transposed weight goes to OpenBLAS GEMV-T (its regular or small-m kernels) or sdot for one
     column (nqk_sgemv_t / nqk_sgemv_small), a one-row MatMul against a row-major weight to GEMV-N
     (nqk_sgemv_n), all restated in oracle/openblas_order.py; every GEMM with M > 1, any K, is
-    reproduced (OpenBLAS's GEMM_Q = 448 K blocks).  So the set is empty unless
-    one_row_restated says otherwise."""
-    from numpy_quant.kernels import one_row_restated
+    reproduced (OpenBLAS's GEMM_Q = 448 K blocks under either driver, and the small-matrix kernels
+    of products of at most 10^6 multiply-adds: kernels.gemm_restated, tests/_sgemm_ref.py) — except a
+    Gemm with transA in the small-matrix regime, whose kernels are not restated.  So the
+    set is empty unless one_row_restated or gemm_restated says otherwise."""
+    from numpy_quant.kernels import one_row_restated, gemm_restated, gemm_small_regime
     bad = set()
     for node in model.nodes:
         ins = [i.name for i in node.inputs]
@@ -113,6 +115,14 @@ def tainted_values(model):
                 n = w.dev.shape[0] if gemm_t else w.dev.shape[-1]
                 covered = one_row_restated(n, a.dev.shape[-1])
                 if not covered:
+                    bad.update(o.name for o in node.outputs)
+            elif a.dev.ndim >= 2 and getattr(w, "dev", None) is not None and w.dev.ndim >= 2:
+                trans_a = node.op == "Gemm" and bool(node.attrs.get("transA"))
+                trans_b = (node.op == "Gemm" and bool(node.attrs.get("transB"))) or bool(getattr(w, "tview", False))
+                M = a.dev.shape[-1] if trans_a else a.dev.shape[-2]
+                K = a.dev.shape[-2] if trans_a else a.dev.shape[-1]
+                N = w.dev.shape[0] if (node.op == "Gemm" and node.attrs.get("transB")) else w.dev.shape[-1]
+                if N >= 2 and (not gemm_restated(M, N, K, trans_b) or (trans_a and gemm_small_regime(M, N, K, False))):
                     bad.update(o.name for o in node.outputs)
         if any(i in bad for i in ins):
             bad.update(o.name for o in node.outputs)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from _sgemm_ref import blas_blocks, _fma_chain_blocks, gemm_driver
 from numpy_quant import onnx_proto
 from numpy_quant.kernels import batch_map
 from numpy_quant.device import collapse, contiguous_strides, broadcast_strides, _Pool
@@ -88,19 +89,6 @@ def test_reshape_target_and_pool_rounding():
     assert _Pool.round(3 << 20) >= 3 << 20
 
 
-def blas_blocks(K, Q=448, U=2):
-    out, ls = [], 0
-    while ls < K:
-        m = K - ls
-        if m >= 2 * Q:
-            m = Q
-        elif m > Q:
-            m = ((m // 2 + U - 1) // U) * U
-        out.append(m)
-        ls += m
-    return out
-
-
 def test_blas_blocking_rule_matches_numpy_dot():
     """The block structure nqk_sgemm uses (OpenBLAS level-3 K loop, GEMM_Q = 448)."""
     assert blas_blocks(768) == [384, 384]
@@ -109,25 +97,15 @@ def test_blas_blocking_rule_matches_numpy_dot():
     assert blas_blocks(64) == [64]
     assert blas_blocks(3072) == [448] * 5 + [416, 416]
     assert blas_blocks(1536) == [448, 448, 320, 320]
+    # an odd half: the threaded driver's ceiling half (the single-thread driver: a multiple of 16)
+    assert blas_blocks(449) == [225, 224] and blas_blocks(449, "single") == [224, 225]
+    assert blas_blocks(450) == [225, 225] and blas_blocks(450, "single") == [240, 210]
+    assert blas_blocks(897) == [448, 225, 224] and blas_blocks(897, "single") == [448, 224, 225]
+    assert blas_blocks(898) == [448, 225, 225] and blas_blocks(898, "single") == [448, 240, 210]
+    assert blas_blocks(1001) == [448, 277, 276] and blas_blocks(1001, "single") == [448, 288, 265]
 
 
-def _fma_chain_blocks(a, w, K):
-    """Per output element: a k-ordered f32 fma chain from 0 in every BLAS block, block
-    results added in order (a*b is exact in f64 for f32 operands; one f64 add then the
-    f32 rounding stands in for the fused rounding)."""
-    f32 = lambda x: x.astype(np.float32).astype(np.float64)  # noqa: E731
-    acc = np.zeros((a.shape[0], w.shape[1]))
-    ls = 0
-    for m in blas_blocks(K):
-        c = np.zeros_like(acc)
-        for k in range(ls, ls + m):
-            c = f32(a[:, k:k + 1] * w[k:k + 1, :] + c)
-        acc = f32(acc + c)
-        ls += m
-    return acc
-
-
-@pytest.mark.parametrize("K", [384, 768, 1000, 3072])
+@pytest.mark.parametrize("K", [384, 768, 1000, 3072, 449, 450, 897, 898, 1001])
 def test_blas_order_matches_numpy_matmul(K):
     """nqk_sgemm's summation order (GEMM_Q = 448 K blocks, k-ordered fma chains) is the
     order of the NumPy the reference runs on (scipy-openblas 0.3.29, SkylakeX kernels):
@@ -142,8 +120,9 @@ def test_blas_order_matches_numpy_matmul(K):
     W = (0.02 * rng.standard_normal((K, 64))).astype(np.float32)
     C = A @ W
     rows, cols = np.arange(0, 40, 5), np.arange(0, 64, 9)
-    got = _fma_chain_blocks(A[rows].astype(np.float64), W[:, cols].astype(np.float64), K)
-    np.testing.assert_array_equal(got.astype(np.float32), C[np.ix_(rows, cols)])
+    driver = gemm_driver(40, 64, K, info[0]["num_threads"])
+    got = _fma_chain_blocks(A[rows], W[:, cols], K, driver)
+    np.testing.assert_array_equal(got, C[np.ix_(rows, cols)])
 
 
 def _proto_view(m):

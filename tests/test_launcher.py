@@ -32,7 +32,15 @@ def test_launcher_spawns_world2_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"],
                        capture_output=True, text=True, timeout=180, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
-    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    # the two ranks share the pipe, and a rank's line and its newline can arrive as two writes:
+    # '{...}{...}\n\n' has been seen, so read every object of a line, not one per line
+    lines, dec = [], json.JSONDecoder()
+    for l in r.stdout.splitlines():
+        while l.startswith("{"):
+            d, end = dec.raw_decode(l)
+            lines.append(d)
+            l = l[end:].lstrip()
+    assert len(lines) == 2
     by = {d["rank"]: d for d in lines}
     assert set(by) == {0, 1}
     for rk, d in by.items():
