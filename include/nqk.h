@@ -267,6 +267,33 @@ int nqk_im2col(const float* x, float* cols, int64_t n, int64_t c, int64_t h, int
                int64_t kh, int64_t kw, int64_t ph0, int64_t pw0, int64_t sh, int64_t sw,
                int64_t ho, int64_t wo);
 
+/* ------------------------- the Conv in integers (opt-in: QModel.integer_conv) */
+/* The integer twin of nqk_im2col (numpy_helper.py:18-70 on the QUANTIZED input): x NCHW and
+ * cols[n*ho*wo][kh*kw*c] (column order kh, kw, c) both in storage `dtype` (NQK_I8 .. NQK_I64);
+ * padded cells hold `pad` (the input's zero point, which dequantizes to exactly 0.0 — the
+ * float Conv's padding; 0 without one).  rowsum (or NULL): int64 [n*ho*wo], the sums of the
+ * rows of cols — the rowsum(A) term of q_matmul's zero point (numpy_quantization.py:49-61). */
+int nqk_im2col_q(const void* x, void* cols, int dtype, int64_t* rowsum, int64_t n, int64_t c, int64_t h,
+                 int64_t w, int64_t kh, int64_t kw, int64_t ph0, int64_t pw0, int64_t sh, int64_t sw,
+                 int64_t ho, int64_t wo, int64_t pad);
+/* The ViT patch embedding of a quantized image in integers, on v_mfma_i32_16x16x64_i8: q_matmul
+ * (numpy_quantization.py:44-61) of the patches of q (numpy_helper.py:18-70; stride = kernel, no
+ * padding) with the int8 weights, dequantized as nqk_dequantize does (numpy_quantization.py:37-41),
+ * then nqk_embed_q's epilogue (tensor.py:328-336 bias add, model.py Reshape / Transpose / Concat /
+ * Add(pos), in the node loop's rounding order):
+ *   acc[b*hw+t][n] = sum_k patch[b*hw+t][k] * wt[n][k]              (int32, exact)
+ *   y              = f32( f64(acc - colterm[n]) * f64(scale) )
+ *   out[b][0][n]   = cls[n] + pos[0][n],   out[b][1+t][n] = (y + bias[n]) + pos[1+t][n].
+ * q: int8 [images][c][h][w]; wt: int8 [N][K], K = c*16*16 in the order (ci, ki, kj), i.e. the
+ * Conv weight [N][c][16][16] as it lies, with no zero point; colterm: int32 [N] = zx * sum_k wt[n][k]
+ * (zx: the image's zero point, 0 without one); scale = f32(sx * sw).  w_l1max: max_n sum_k |wt[n][k]|,
+ * or -1 when unknown: the dequantize runs in f32 only where max|x - zx| * w_l1max < 2^24 proves
+ * f32(acc - colterm) exact, else it takes the f64 product.  Refused: unaligned operands (16 bytes),
+ * kh, kw != 16, h % 16, w % 16, N % 64, |zx| > 2^20, K 2^14 + |zx| K 2^7 >= 2^31. */
+int nqk_embed_qi8(const int8_t* q, const int8_t* wt, const int32_t* colterm, float scale, int64_t zx,
+                  int64_t w_l1max, const float* bias, const float* cls, const float* pos, float* out,
+                  int64_t images, int64_t c, int64_t h, int64_t w, int64_t kh, int64_t kw, int64_t N);
+
 /* ------------------------------------------- float ops (model.py:65-213) */
 enum nqk_binop { NQK_ADD = 0, NQK_SUB = 1, NQK_MUL = 2, NQK_DIV = 3 };
 /* out[i] = a[ia] op b[ib] over an N-d broadcast (ndim <= 6; strides in elements) */

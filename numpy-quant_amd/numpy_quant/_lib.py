@@ -131,6 +131,8 @@ SIGNATURES = {
     "nqk_patchify_dequant": [_p, _p, _l, _l, _l, _l, _l, _l, _f, _l],
     "nqk_embed_weight_order": [],
     "nqk_embed_q": [_p, _f, _l, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l],
+    "nqk_im2col_q": [_p, _p, _i, _p] + [_l] * 13,
+    "nqk_embed_qi8": [_p, _p, _p, _f, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l],
     "nqk_comm_unique_id": [_p],
     "nqk_comm_init": [_p, _i, _i],
     "nqk_comm_bcast": [_p, ctypes.c_size_t, _i],

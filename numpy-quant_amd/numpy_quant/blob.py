@@ -93,6 +93,9 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
     header = {"version": 1, "bit_width": int(qmodel.bit_width),
               "qparams": {k: _enc_qp(p) for k, p in qmodel.quant_params.items()},
               "constants": entries, "payload_bytes": off}
+    if getattr(qmodel, "integer_conv", False):
+        # written only when set: a model saved without the flag keeps its bytes (a missing key is False)
+        header["integer_conv"] = True
     return header, payload
 
 
@@ -130,7 +133,8 @@ def attach(model, header: dict, payload: DeviceArray):
         raise ValueError(f"unsupported blob version {header.get('version')}")
     qp = qparams_from(header)
     consts = constants_from(header, payload)
-    return model._rewrite(header["bit_width"], lambda value, asym: qp[value.name], constants=consts)
+    return model._rewrite(header["bit_width"], lambda value, asym: qp[value.name], constants=consts,
+                          integer_conv=bool(header.get("integer_conv", False)))
 
 
 def encode_header(header: dict) -> bytes:

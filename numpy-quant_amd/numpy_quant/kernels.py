@@ -764,3 +764,79 @@ def im2col(x: DeviceArray, kh, kw, pads, strides):
     cols = DeviceArray((n * ho * wo, kh * kw * c), np.float32)
     _lib.call("nqk_im2col", x.vp, cols.vp, n, c, h, w, kh, kw, ph0, pw0, sh, sw, ho, wo)
     return cols, ho, wo
+
+
+# ----------------------------------------------------------------------------- integer Conv
+def _inside(arr: DeviceArray) -> bool:
+    return arr.ptr >= arr.block.ptr and arr.ptr + arr.nbytes <= arr.block.ptr + arr.block.size
+
+
+def im2col_q(x: DeviceArray, kh, kw, pads, strides, pad: int = 0, rowsum: bool = False):
+    """`im2col` of integer storage (nqk_im2col_q): `(cols, row sums | None, ho, wo)`, cols in x's
+    dtype with padded cells = `pad` (the zero point); the int64 row sums are cols.sum(1).  Every
+    argument is checked here, before the library is touched."""
+    if not isinstance(x, DeviceArray) or x.ndim != 4:
+        raise ValueError("im2col_q: a 4-d (NCHW) DeviceArray expected")
+    if x.dtype not in (np.int8, np.int16, np.int32, np.int64):
+        raise ValueError(f"im2col_q: dtype {x.dtype} not supported (int8 / int16 / int32 / int64)")
+    n, c, h, w = x.shape
+    kh, kw = int(kh), int(kw)
+    ph0, pw0, ph1, pw1 = (int(p) for p in pads)
+    sh, sw = (int(s) for s in strides)
+    if kh < 1 or kw < 1 or sh < 1 or sw < 1 or min(ph0, pw0, ph1, pw1) < 0:
+        raise ValueError("im2col_q: kernel and strides of at least 1 and non-negative pads expected")
+    pad = int(pad)
+    info = np.iinfo(x.dtype)
+    if not info.min <= pad <= info.max:
+        raise ValueError(f"im2col_q: the pad value {pad} does not fit {x.dtype}")
+    ho = max(0, (h - kh + ph0 + ph1) // sh + 1)
+    wo = max(0, (w - kw + pw0 + pw1) // sw + 1)
+    if not _inside(x):
+        raise ValueError("im2col_q: x reaches outside its buffer")
+    cols = DeviceArray((n * ho * wo, kh * kw * c), x.dtype)
+    rs = DeviceArray((n * ho * wo,), np.int64) if rowsum else None
+    _lib.call("nqk_im2col_q", x.vp, cols.vp, x.code, rs.vp if rs is not None else None, n, c, h, w, kh, kw, ph0,
+              pw0, sh, sw, ho, wo, pad)
+    return cols, rs, ho, wo
+
+
+EMBED_QI8_MAX_ZP = 1 << 20
+
+
+def embed_qi8_fits(images: int, c: int, h: int, w: int, kh: int, kw: int, kout: int, zx) -> bool:
+    """Whether nqk_embed_qi8 takes the shape (its own refusals, include/nqk.h)."""
+    zx = 0 if zx is None else int(zx)
+    kk = c * kh * kw
+    return (kh == 16 and kw == 16 and h > 0 and w > 0 and h % 16 == 0 and w % 16 == 0 and kk % 64 == 0 and kout > 0 and
+            kout % 64 == 0 and abs(zx) <= EMBED_QI8_MAX_ZP and kk * (1 << 14) + abs(zx) * kk * (1 << 7) < (1 << 31) and
+            images <= 1 << 24 and kout <= 1 << 24 and h <= 1 << 20 and w <= 1 << 20 and
+            -(-(images * (h // 16) * (w // 16)) // 128) * (kout // 64) <= 2147483647)
+
+
+def embed_qi8(q: DeviceArray, wt: DeviceArray, colterm: DeviceArray, scale, zx, w_l1max: int, bias: DeviceArray,
+              cls: DeviceArray, pos: DeviceArray, out: DeviceArray) -> None:
+    """nqk_embed_qi8 (include/nqk.h) into `out` [images][hw + 1][N]: q int8 [images][c][h][w] in
+    16 x 16 patches, wt int8 [N][c * 256] (the Conv weight as it lies), colterm int32 [N] =
+    zx * wt.sum(1).  Every extent is checked here against its buffer, before the library is
+    touched; the library checks alignment and the value ranges again."""
+    for arr, what, dt in ((q, "q", np.int8), (wt, "wt", np.int8), (colterm, "colterm", np.int32),
+                          (bias, "bias", np.float32), (cls, "cls", np.float32), (pos, "pos", np.float32),
+                          (out, "out", np.float32)):
+        if not isinstance(arr, DeviceArray) or arr.dtype != dt:
+            raise ValueError(f"embed_qi8: {what} must be a {np.dtype(dt)} DeviceArray")
+        if not _inside(arr):
+            raise ValueError(f"embed_qi8: {what} reaches outside its buffer")
+    if q.ndim != 4 or wt.ndim != 2:
+        raise ValueError("embed_qi8: q [images][c][h][w] and wt [N][K] expected")
+    n, c, h, w = q.shape
+    kout, kk = wt.shape
+    if kk != c * 256:
+        raise ValueError(f"embed_qi8: wt has K = {kk}, the image needs {c * 256}")
+    if not embed_qi8_fits(n, c, h, w, 16, 16, kout, zx):
+        raise ValueError(f"embed_qi8: shape not taken (images {n}, c {c}, {h} x {w}, N {kout}, zero point {zx})")
+    hw = (h // 16) * (w // 16)
+    if colterm.size != kout or bias.size != kout or cls.size != kout or pos.size != (hw + 1) * kout or \
+            out.size != n * (hw + 1) * kout:
+        raise ValueError("embed_qi8: colterm / bias / cls [N], pos [hw + 1][N] and out [images][hw + 1][N] expected")
+    _lib.call("nqk_embed_qi8", q.vp, wt.vp, colterm.vp, float(np.float32(scale)), 0 if zx is None else int(zx),
+              int(w_l1max), bias.vp, cls.vp, pos.vp, out.vp, n, c, h, w, 16, 16, kout)

@@ -25,7 +25,7 @@ from . import onnx_proto
 from .device import DeviceArray, sync
 from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
-from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, quantize_tensor, where)
+from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, qconv2d, quantize_tensor, where)
 from . import kernels as K
 
 
@@ -219,6 +219,26 @@ def onnx_operator_implementation(op: str, inputs: list[Tensor], attrs: dict[str,
     return fn(inputs, attrs)
 
 
+def integer_conv_eligible(node) -> bool:
+    """Whether a Conv node takes the integer path when QModel.integer_conv is set: a quantized
+    input with a scalar zero point or none, a quantized constant weight, a bias, dilation 1 and
+    group 1.  Every other Conv keeps the float path."""
+    if node.op != "Conv" or len(node.inputs) != 3:
+        return False
+    x, w, b = (i.data for i in node.inputs)
+    if not isinstance(x, QTensor) or not isinstance(w, QTensor) or not isinstance(node.inputs[1], Constant):
+        return False
+    if not isinstance(b, (QTensor, FTensor)):
+        return False
+    for t in (x, w):
+        if t._bias is not None or isinstance(t._zero_point, K.ZpTerm) or t.dev.ndim != 4:
+            return False
+    a = node.attrs
+    if any(int(d) != 1 for d in a.get("dilations", [1, 1])) or int(a.get("group", 1)) != 1:
+        return False
+    return "pads" in a and "strides" in a
+
+
 # ----------------------------------------------------------------------------- models
 class Model:
     def __init__(self, nodes: list[Node], values: list[Value], inputs: List[Variable], outputs: List[Variable]):
@@ -355,15 +375,17 @@ class Model:
                 vmin[val.name], vmax[val.name] = np.mean(flat.min()), np.mean(flat.max())
         return vmin, vmax
 
-    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8):
-        """Calibration + graph rewrite (model.py:328-442)."""
+    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False):
+        """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
+        reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
+        (QModel.integer_conv)."""
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool):
             s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -384,7 +406,7 @@ class Model:
             raise ValueError("calibrate_stream: no calibration batch")
         return cal.ranges()
 
-    def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False):
+    def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`."""
         vmin, vmax = self.calibrate_stream(batches, percentile, clip_weights)
 
@@ -392,7 +414,7 @@ class Model:
             s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -449,11 +471,11 @@ class Model:
         states = cmp.states()
         return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
 
-    def quantize_with(self, quant_params: dict, bit_width=8):
+    def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
         skipping the calibration forward."""
-        return self._rewrite(bit_width, lambda value, asym: quant_params[value.name])
+        return self._rewrite(bit_width, lambda value, asym: quant_params[value.name], integer_conv=integer_conv)
 
     def load_quantized(self, path):
         """The QModel saved by `QModel.save(path)` (blob.py) on this model's graph:
@@ -461,7 +483,7 @@ class Model:
         from . import blob
         return blob.load(self, path)
 
-    def _rewrite(self, bit_width, params, constants=None):
+    def _rewrite(self, bit_width, params, constants=None, integer_conv=False):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here."""
         constants = constants or {}
@@ -554,6 +576,7 @@ class Model:
         qinputs = [qvalues[i.name] for i in self.inputs]
         qmodel = QModel(list(qnodes.values()), list(qvalues.values()), qinputs, qoutputs, bit_width, qp)
         qmodel.image_preprocess = self.image_preprocess
+        qmodel.integer_conv = bool(integer_conv)
         return qmodel
 
 
@@ -570,6 +593,11 @@ class QModel(Model):
         # intermediate value.data is populated (reference test/test_mlp.py:159-168)
         self.fuse = os.environ.get("NQK_FUSE", "1") != "0"
         self.keep_values = False
+        # opt-in, not the reference's behaviour: a Conv whose input and weight are quantized
+        # multiplies them in integers (tensor.qconv2d: q_matmul on the im2col of the quantized
+        # input) instead of dequantizing both for the float Conv.  Set it before the first call:
+        # the fused plan reads it when it is compiled.
+        self.integer_conv = False
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "
@@ -724,6 +752,8 @@ class QModel(Model):
     def _run_node(self, node, times, profile=False):
         """One iteration of the node loop of QModel.__call__ (model.py:502-550)."""
         args = []
+        if self.integer_conv and node.op == "Conv" and integer_conv_eligible(node):
+            return self._run_qconv(node, times, profile)
         if node.op in ("MatMul", "Gemm"):
             for i in node.inputs:
                 if isinstance(i.data, FTensor):
@@ -758,6 +788,24 @@ class QModel(Model):
             times[node.op] += time() - t0
         for o, tensor in zip(node.outputs, outs):
             o.data = tensor
+
+    def _run_qconv(self, node, times, profile=False):
+        """An eligible Conv with integer_conv set: input and weight stay quantized (qconv2d), the
+        bias is the dequantized float constant of the float path; timed under "Conv"."""
+        x, w, b = node.inputs
+        t0 = time()
+        bias = self._dequant_input(b) if isinstance(b.data, QTensor) else b.data
+        if profile:
+            sync()
+        if times is not None:
+            times["TinyqDequant"] += time() - t0
+        t0 = time()
+        out = qconv2d(x.data, w.data, bias, tuple(node.attrs["pads"]), tuple(node.attrs["strides"]))
+        if profile:
+            sync()
+        if times is not None:
+            times["Conv"] += time() - t0
+        node.outputs[0].data = out
 
     def run(self, profile=False, eager=False):
         """The node loop of QModel.__call__ (model.py:497-550) on device tensors,

@@ -450,6 +450,65 @@ class FusedEmbed:
         self.wt = None
         if (cin == 3 and m.kh == 16 and m.kw == 16 and self.kout % 64 == 0 and os.environ.get("NQK_EMBED_Q", "1") != "0"):
             self.wt = embed_weight_image(W, self.kout, self.kk)
+        # QModel.integer_conv: the Conv in integers.  nqk_embed_qi8 where it applies (int8 weight
+        # without a zero point, 16 x 16 patches, N % 64 == 0): the weight [N][c][16][16] as it lies,
+        # its column sums and max_n sum_k |w| (what proves the f32 dequantize exact); otherwise
+        # the node loop's own qconv2d.  Same bits either way: an integer sum has no order.
+        self.integer = bool(getattr(qmodel, "integer_conv", False))
+        self.qi8 = None
+        self._colterms = {}
+        wq = m.w.data
+        if (self.integer and isinstance(wq, QTensor) and wq.dev.dtype == np.int8 and wq._zero_point is None and
+                wq._bias is None and m.kh == 16 and m.kw == 16 and self.kout % 64 == 0):
+            host = wq.dev.to_host().astype(np.int64).reshape(self.kout, self.kk)
+            self.qi8 = (wq.dev.reshape((self.kout, self.kk)), host.sum(1), int(np.abs(host).sum(1).max()))
+            p = qmodel.quant_params.get(m.x.name)
+            if p is not None and (p.zero_point is None or np.ndim(p.zero_point) == 0):
+                self._colterm(None if p.zero_point is None else int(p.zero_point))  # uploaded now, not in a capture
+
+    def _colterm(self, zx):
+        """int32 [N] zx * colsum(W) on the device, per zero point seen"""
+        ct = self._colterms.get(zx)
+        if ct is None:
+            v = self.qi8[1] * np.int64(0 if zx is None else zx)
+            if v.size and (v.min() < -(1 << 31) or v.max() >= 1 << 31):
+                return None
+            ct = self._colterms[zx] = DeviceArray.from_host(v.astype(np.int32))
+        return ct
+
+    def _run_integer(self, qmodel, streams, xd, n, c, h, w, hw):
+        """run() with QModel.integer_conv on a quantized image."""
+        m = self.m
+        zx = xd.zp_scalar
+        ct = None
+        if (self.qi8 is not None and xd.dev.dtype == np.int8 and
+                KM.embed_qi8_fits(streams.max_part(n), c, h, w, m.kh, m.kw, self.kout, zx)):
+            ct = self._colterm(zx)
+        if ct is None:
+            from .tensor import qconv2d, concat
+            streams.join()
+            y = qconv2d(xd, m.w.data, FTensor(self.bias), (0, 0, 0, 0), (m.kh, m.kw))
+            y = FTensor(y.dev.reshape((n, self.kout, hw))).transpose([0, 2, 1])
+            cls = FTensor(self.cls).expand(m.expand.inputs[1].data)
+            m.add.outputs[0].data = concat([cls, y], 1) + FTensor(self.posv)
+            m.conv_out.data = FusedAway(m.conv_out.name)
+            return
+        wt, _, l1 = self.qi8
+        scale = np.float32(xd.scale) * np.float32(m.w.data.scale)
+        out = DeviceArray((n, hw + 1, self.kout), np.float32)
+        t0 = KM.TIMER.begin() if KM.TIMER is not None else None
+
+        def part(s_idx, i0, nb):
+            qv = xd.dev.offset_view(i0 * c * h * w, (nb, c, h, w))
+            ov = out.offset_view(i0 * (hw + 1) * self.kout, (nb, hw + 1, self.kout))
+            KM.embed_qi8(qv, wt, ct, scale, zx, l1, self.bias, self.cls, self.posv, ov)
+
+        streams.halves(n, part)
+        if t0 is not None:
+            KM.TIMER.end("embed_qi8", t0, (2 * n * hw * self.kk * self.kout,
+                                           n * c * h * w + self.kk * self.kout + 4 * n * (hw + 1) * self.kout))
+        m.add.outputs[0].data = FTensor(out)
+        m.conv_out.data = FusedAway(m.conv_out.name)
 
     def pre(self, qmodel):
         """at the Conv's position: the shape-only placeholder for the Shape consumer"""
@@ -473,6 +532,9 @@ class FusedEmbed:
         eshape = np.asarray(m.expand.inputs[1].data.data).reshape(-1)
         if eshape.size != 3 or int(eshape[0]) != n:
             raise ValueError(f"class-token Expand shape {eshape} does not match the batch {n}")
+        if (self.integer and isinstance(xd, QTensor) and xd._bias is None and not isinstance(xd._zero_point, KM.ZpTerm) and
+                h % m.kh == 0 and w % m.kw == 0):
+            return self._run_integer(qmodel, streams, xd, n, c, h, w, hw)
         if KM.gemm_small_regime(n * hw, self.kout, self.kk):
             # np.matmul takes OpenBLAS's small-matrix kernels for this Conv (no K blocking, dot-product
             # column tails): the embedding kernels keep the level-3 order, so the node loop's own

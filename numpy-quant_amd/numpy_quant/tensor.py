@@ -449,6 +449,65 @@ def fconv2d(x: FTensor, w: FTensor, b: FTensor, pads, strides):
     return FTensor(out)
 
 
+def conv_weight_operand(w: QTensor):
+    """(wm [K, N], Bt [N, Kp] | None, colsum int64 [N]) of a quantized Conv weight [N][c][kh][kw] in
+    im2col's column order (ki, kj, ci); computed once per weight."""
+    ops = getattr(w, "_conv_ops", None)
+    if ops is None:
+        kout, c, kh, kw = w.dev.shape
+        kk = kh * kw * c
+        wm = permute(w.dev, [2, 3, 1, 0]).reshape((kk, kout))
+        if w.dev.dtype == np.int8:
+            bt, col = K.weight_bt(wm)
+        else:
+            bt, col = None, K.rowsum(w.dev, 1, kout, kk, kk, 0)  # a sum has no order: the weight as it lies
+        ops = w._conv_ops = (wm, bt, col)
+    return ops
+
+
+def qconv2d(x: QTensor, w: QTensor, b: FTensor, pads, strides):
+    """Conv(x, W, b) in integers (QModel.integer_conv): the reference's q_matmul
+    (numpy_quantization.py:44-61) applied to its im2col (numpy_helper.py:18-70) of the quantized
+    input — padded cells hold x's zero point, which dequantizes to exactly 0.0 — then the
+    dequantize (numpy_quantization.py:37-41) with the zero-point term and fconv2d's one float add
+    of the bias (tensor.py:328-336).  Any bit width; x and W with a scalar zero point or none."""
+    if not isinstance(x, QTensor) or not isinstance(w, QTensor) or not isinstance(b, FTensor):
+        raise ValueError("qconv2d: QTensor input and weight and a float bias expected")
+    if x._bias is not None or w._bias is not None:
+        raise ValueError("qconv2d: a biased Gemm accumulator is not a Conv operand")
+    n, c, h, wd = x.dev.shape
+    kout, c2, kh, kw = w.dev.shape
+    if c != c2:
+        raise ValueError("Conv channel mismatch")
+    if b.dev.size != kout:
+        raise ValueError(f"Conv bias of {b.dev.size} elements for {kout} output channels")
+    zx, zw = x.zp_scalar, w.zp_scalar
+    cols, rs, ho, wo = K.im2col_q(x.dev, kh, kw, tuple(int(p) for p in pads), tuple(int(s) for s in strides),
+                                  pad=0 if zx is None else zx, rowsum=zw is not None)
+    kk = kh * kw * c
+    rows = n * ho * wo
+    wm, bt, col = conv_weight_operand(w)
+    acc, _ = K.qmatmul(cols, wm, None, None, bt, None)  # [rows, kout]; the zero-point term from the sums at hand
+    zt = None
+    if zx is not None or zw is not None:
+        flags = (_lib.ZP_COL if zx is not None else 0) | (_lib.ZP_ROW if zw is not None else 0)
+        if zx is not None and zw is not None:
+            flags |= _lib.ZP_KCONST
+        _, bmap = K.batch_map((), ())
+        zt = K.ZpTerm(flags, 0 if zx is None else zx, 0 if zw is None else zw, kk, rs,
+                      col if zx is not None else None, bmap, (), (), rows, kout)
+    y = K.dequantize(acc, np.float32(x.scale) * np.float32(w.scale), zt)
+    # NHWC -> NCHW fused with the bias add, as fconv2d
+    out_shape = (n, kout, ho, wo)
+    y_st = [ho * wo * kout, 1, wo * kout, kout]
+    out = DeviceArray(out_shape, np.float32)
+    from .device import collapse
+    shp, (sa, sb) = collapse(out_shape, y_st, [0, 1, 0, 0])
+    _lib.call("nqk_binary_f32", _lib.ADD, y.vp, b.dev.vp, out.vp, len(shp), _lib.i64arr(shp), _lib.i64arr(sa),
+              _lib.i64arr(sb))
+    return FTensor(out)
+
+
 # ----------------------------------------------------------------------------- device views
 def take(x: DeviceArray, indices: np.ndarray, axis: int) -> DeviceArray:
     """ndarray.take along one axis (ITensor indices on the host)."""
