@@ -124,6 +124,30 @@ int nqk_requantize(const void* acc, int acc_dtype, const void* bias, int bias_dt
                    const int64_t* row, const int64_t* col, const int64_t* bmap,
                    float res_scale, int64_t res_zp, int has_res_zp, int bit_width);
 
+/* ---- per-column weight scales (opt-in: QModel.per_channel; not the reference's behaviour).
+ * The reference's formulas with a scale vector over the last axis in the scalar's place. */
+/* Exact minimum and maximum of every column of w [rows][ld] (cols <= ld used): the inputs of
+ * quant_parameters (numpy_quantization.py:7-21) applied to one column, as tensor.py:304-308
+ * feeds it the whole tensor's.  out[0][n] = min_k w[k][n], out[1][n] = max_k w[k][n]; a column
+ * that holds a NaN gives NaN for both, as np.min / np.max do.  One pass, one thread per column. */
+int nqk_minmax_cols(const float* w, int64_t rows, int64_t cols, int64_t ld, float* out /* [2][cols] */);
+/* quantize  numpy_quantization.py:24-34 without a zero point, per element with its column's scale:
+ *   q[r][n] = int(rint(clip(f32(x[r][n] / scale[n]), f32(lo), f32(hi)))) */
+int nqk_quantize_cols(const float* x, void* q, int q_dtype, int64_t rows, int64_t cols,
+                      const float* scale /* [cols] */, int bit_width);
+/* dequantize  numpy_quantization.py:37-41:  out = f32( f64(q - zpt) * f64(scale[n]) ) over
+ * out[batch][M][N]; every other argument as nqk_dequantize takes it. */
+int nqk_dequantize_cols(const void* q, int q_dtype, float* out, int64_t batch, int64_t M, int64_t N,
+                        const float* scale /* [N] */, int zp_flags, int64_t zp, int64_t zpa, int64_t zpb,
+                        int64_t K, const int64_t* row, const int64_t* col, const int64_t* bmap /* 5 */);
+/* requantize  numpy_quantization.py:64-72 (+ the Gemm bias, tensor.py:255-259):
+ *   d = f32( f64(acc + bias[n] - zpt) * f64(scale[n]) ), then as nqk_requantize. */
+int nqk_requantize_cols(const void* acc, int acc_dtype, const void* bias, int bias_dtype,
+                        void* out, int out_dtype, int64_t batch, int64_t M, int64_t N,
+                        const float* scale /* [N] */, int zp_flags, int64_t zp, int64_t zpa, int64_t zpb,
+                        int64_t K, const int64_t* row, const int64_t* col, const int64_t* bmap,
+                        float res_scale, int64_t res_zp, int has_res_zp, int bit_width);
+
 /* QTensor.relu  tensor.py:212-215:  out[i] = q[i] < zp ? zp : q[i]  (zp the tensor's scalar
  * zero point; out may be wider than q when zp lies outside q's storage range) */
 int nqk_relu_q(const void* q, int q_dtype, void* out, int out_dtype, int64_t n, int64_t zp);
@@ -436,6 +460,14 @@ typedef struct nqk_epilogue {
   int8_t* ln_out;
   float ln_eps, ln_scale;
   int64_t ln_zp;
+  /* Per-column dequant scales (opt-in: QModel.per_channel), or NULL: s_acc, exactly as before.
+   * float [N], 16-byte aligned: s_col[n] = f32(s_a) * f32(s_w[n]), which replaces s_acc[g] in
+   * d = f32( f64(acc - zpt) * f64(s) ) (numpy_quantization.py:37-41) of the QKV, RESID and GELU
+   * epilogues.  bt is then always the unpacked [N][K] weight: the persistent GEMM's per-column
+   * variant takes the call from bt_pg where it takes the shape (b_packed = 2 names bt_pg as the
+   * nqk_pack_pg4 nibble image, 0 as nqk_pack_pg's), the small-tile kernel from bt otherwise
+   * (nqk_qgemm_last_kernel() says which).  ln_out, or b_packed = 1, beside s_col is refused. */
+  const float* s_col;
 } nqk_epilogue;
 /* int8 MFMA GEMM C = A . Bt^T (layouts as nqk_qgemm_i8) with a fused epilogue:
  *   QKV    model.py MatMul -> Add(bias) -> Reshape -> Transpose -> quantize, 3 groups

@@ -130,14 +130,17 @@ __device__ __forceinline__ int sum16(v4i c) {
 struct EpiCol {
   int64_t colterm;  // col-sum term minus the K constant (fits int32 when the kernel's I32 holds)
   float bias;
+  float s_col;      // the column's dequant scale (nqk_epilogue.s_col), read only when one is given
   int gn, g, hh, dd;
   bool valid;
 };
 
 template <int EPI>
-__device__ __forceinline__ EpiCol epi_col(const Epi& e, int gn, int N, int64_t colsum_b, int64_t kconst) {
+__device__ __forceinline__ EpiCol epi_col(const Epi& e, int gn, int N, int64_t colsum_b, int64_t kconst,
+                                          const float* __restrict__ s_col) {
   EpiCol c;
   c.valid = gn < N;
+  c.s_col = (s_col != nullptr && c.valid) ? s_col[gn] : 0.0f;
   c.gn = gn;
   c.colterm = ((e.zp_flags & NQK_ZP_COL) ? colsum_b * e.zpa : 0) - kconst;
   c.bias = (e.bias != nullptr && c.valid) ? e.bias[gn] : 0.0f;
@@ -156,7 +159,8 @@ __device__ __forceinline__ EpiCol epi_col(const Epi& e, int gn, int N, int64_t c
 // one output element: v = acc - zpt -> dequant -> the consumer chain -> store
 template <int EPI, bool I32>
 __device__ __forceinline__ void epi_elem(const Epi& e, int bz, int gm, int M, int N, int64_t rowterm, int img, int t,
-                                         int img_b, int head_b, const EpiCol& c, int32_t acc, float resid, bool ok) {
+                                         int img_b, int head_b, const EpiCol& c, int32_t acc, float resid, bool ok,
+                                         bool per_col) {
   double vd;
   if constexpr (I32) {
     vd = (double)(acc - (int32_t)rowterm - (int32_t)c.colterm);  // host-checked: no int32 overflow
@@ -164,7 +168,8 @@ __device__ __forceinline__ void epi_elem(const Epi& e, int bz, int gm, int M, in
     vd = (double)((int64_t)acc - rowterm - c.colterm);
   }
   const int g = c.g;
-  const float d = (float)(vd * (double)e.s_acc[g]);
+  // numpy_quantization.py:37-41 with the column's scale in the scalar's place (QModel.per_channel)
+  const float d = (float)(vd * (double)(per_col ? c.s_col : e.s_acc[g]));
   const int gn = c.gn;
   if constexpr (EPI == EPI_SCORES) {
     const float y = div_rc(d, e.div, e.rdiv);
@@ -409,7 +414,8 @@ __device__ __forceinline__ void epi_row4(const Epi& e, int gm, int img, int t, i
 template <int EPI, bool I32>
 __global__ void __launch_bounds__(256)
 k_qgemm_epi(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, int N, int K, int lda, int ldb,
-            BatchMap bm, int64_t a_ms, int64_t b_ms, int tiles_m, int tiles_n, Epi e) {
+            BatchMap bm, int64_t a_ms, int64_t b_ms, int tiles_m, int tiles_n, Epi e,
+            const float* __restrict__ s_col /* [N] per-column dequant scales, or null: e.s_acc */) {
   __shared__ __attribute__((aligned(16))) int8_t smem[2 * (FBM + FBN) * FBK];
 #define AS(buf) (smem + (buf) * (FBM + FBN) * FBK)
 #define BS(buf) (smem + (buf) * (FBM + FBN) * FBK + FBM * FBK)
@@ -513,7 +519,7 @@ k_qgemm_epi(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int nl = wn * 64 + j * 32 + r32;
-    cols[j] = epi_col<EPI>(e, n0 + nl, N, need_rb ? (int64_t)rsB[nl] : 0, kconst);
+    cols[j] = epi_col<EPI>(e, n0 + nl, N, need_rb ? (int64_t)rsB[nl] : 0, kconst, s_col);
   }
   int img_b = 0, head_b = 0;
   if constexpr (EPI == EPI_PV) {
@@ -547,7 +553,7 @@ k_qgemm_epi(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int M, 
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         epi_elem<EPI, I32>(e, bz, gm, M, N, rowterm, img, t, img_b, head_b, cols[j], acc[i][j][r], res[r][j],
-                      rok && cols[j].valid);
+                      rok && cols[j].valid, s_col != nullptr);
     }
   }
 }
@@ -1936,6 +1942,21 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
   if (params->zp_flags & (NQK_ZP_SCALAR | NQK_ZP_FULL))
     return fail("nqk_qgemm_fused: only row / column / K-constant zero-point terms");
   const Epi e = make_epi(params);
+  // per-column dequant scales (QModel.per_channel): the small-tile kernel reads them; the big-tile,
+  // k_proj and persistent kernels take one scale per column group and are passed by
+  const float* s_col = params->s_col;
+  if (s_col != nullptr) {
+    if (((uintptr_t)s_col) & 15) return fail("nqk_qgemm_fused: s_col must be 16-byte aligned");
+    if (!(epi == EPI_QKV || epi == EPI_RESID || epi == EPI_GELU))
+      return fail("nqk_qgemm_fused: s_col belongs to the QKV, RESID and GELU epilogues");
+    if (params->ln_out != nullptr)
+      return fail("nqk_qgemm_fused: a fused LayerNorm (ln_out) does not combine with per-column scales (s_col)");
+    // bt is the unpacked [N][K] weight (the small-tile kernel's operand where k_pg declines the
+    // case); b_packed then only names bt_pg's format: 0 nqk_pack_pg, 2 the nqk_pack_pg4 nibble image
+    if (params->b_packed == 1)
+      return fail("nqk_qgemm_fused: with per-column scales bt is the unpacked weight; there is no big-tile kernel "
+                  "for an nqk_pack_b image (b_packed = 1)");
+  }
   // int32 zero-point algebra when |acc| + |row term| + |col term| + |K term| < 2^31
   const double za = (double)(params->zpa < 0 ? -params->zpa : params->zpa);
   const double zb = (double)(params->zpb < 0 ? -params->zpb : params->zpb);
@@ -1964,7 +1985,7 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
       return fail("nqk_qgemm_fused: a fused LayerNorm needs the residual epilogue at N = 192 on the big-tile path "
                   "(16-byte aligned gamma / beta, a normal ln_scale)");
   }
-  if (params->b_packed && !(big && aligned && scales_ok && (K % (GST * GBK)) == 0))
+  if (params->b_packed && s_col == nullptr && !(big && aligned && scales_ok && (K % (GST * GBK)) == 0))
     return fail("nqk_qgemm_fused: a packed B operand needs the big-tile path (K % 192 == 0, N % 4 == 0, "
                 "COL zero-point term, aligned outputs)");
   if (big && aligned && scales_ok) {
@@ -1992,6 +2013,7 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
         return 0;
       }
     }
+    if (s_col == nullptr) {  // (per-column scales: k_pg above or the small-tile kernel below)
     // the persistent 256 x 256 kernel where it takes the shape: QKV by default; FFN-up +
     // GELU with NQK_PROJ_GELU=1 and the residual epilogues with NQK_PROJ_RESID=1 (faster
     // alone, not inside the two-stream forward, DESIGN.md "Projection GEMM variants");
@@ -2037,6 +2059,7 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
     }
     g_last_gemm = 1;
     return launch_status("nqk_qgemm_fused(big)");
+    }
   }
   g_last_gemm = 0;
   const int tiles_m = (int)((M + FBM - 1) / FBM), tiles_n = (int)((N + FBN - 1) / FBN);
@@ -2044,9 +2067,9 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
   const dim3 grid(tiles_m * tiles_n, 1, (unsigned)batch);
   switch (epi) {
 #define L(E) case E: if (i32) hipLaunchKernelGGL((k_qgemm_epi<E, true>), grid, dim3(256), 0, stream(), a, bt, (int)M, \
-                                 (int)N, (int)K, (int)lda, (int)ldb, m, a_mat_stride, b_mat_stride, tiles_m, tiles_n, e); \
+                                 (int)N, (int)K, (int)lda, (int)ldb, m, a_mat_stride, b_mat_stride, tiles_m, tiles_n, e, s_col); \
                       else hipLaunchKernelGGL((k_qgemm_epi<E, false>), grid, dim3(256), 0, stream(), a, bt, (int)M, \
-                                 (int)N, (int)K, (int)lda, (int)ldb, m, a_mat_stride, b_mat_stride, tiles_m, tiles_n, e); break;
+                                 (int)N, (int)K, (int)lda, (int)ldb, m, a_mat_stride, b_mat_stride, tiles_m, tiles_n, e, s_col); break;
     L(EPI_QKV) L(EPI_SCORES) L(EPI_PV) L(EPI_RESID) L(EPI_GELU) L(EPI_NULL)
 #undef L
     default: return fail("nqk_qgemm_fused: unknown epilogue");

@@ -96,6 +96,9 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   if (b4 && !(p->bit_width <= 4 && p->col_absmax > 0 && 16.0 * (double)p->col_absmax * (double)llabs(p->zpa) < 2147483647.0))
     return 0;
   if (!(epi == PG_QKV || epi == PG_RESID || epi == PG_GELU)) return 0;
+  // per-column dequant scales (nqk_epilogue.s_col): the PC instances (WM = 1)
+  const bool pc = p->s_col != nullptr;
+  if (pc && (((uintptr_t)p->s_col) & 15)) return 0;
   // K = 192 / 768 / 3072 (ViT-Ti / ViT-B widths and MLP), N % 64 == 0 (a partial last column
   // tile: whole waves past N)
   if (!(K == 192 || K == 768 || K == 3072) || N % 64 != 0 || M < PG_BM) return 0;
@@ -116,7 +119,7 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   int wm = 1;
   {
     const char* wv = getenv("NQK_PG_WM");
-    if (wv) wm = atoi(wv) == 2 ? 2 : 1;
+    if (wv && !pc) wm = atoi(wv) == 2 ? 2 : 1;
     if (wm == 2 && (K == 192 || M < 2 * PG_BM || (epi == PG_RESID && M % (2 * PG_BM) != 0 && p->resid == p->out[0])))
       wm = 1;
   }
@@ -130,7 +133,7 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   bool glut = epi == PG_GELU && p->gelu_lut != nullptr && p->lut_n > 0 && p->lut_n <= GLUT_MAX &&
               (((uintptr_t)p->gelu_lut) & 15) == 0 && !getenv("NQK_NO_GLUT");
   if (glut && p->lut_n > GLUT_CAP1) {
-    if (M >= 2 * PG_BM && !b4 && f32x && (K == 192 || K == 768)) wm = 2;
+    if (M >= 2 * PG_BM && !b4 && f32x && (K == 192 || K == 768) && !pc) wm = 2;
     else glut = false;
   }
   if (p->bit_width < 2 || p->bit_width > 8) return 0;  // int8 outputs
@@ -174,6 +177,7 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   e.mul2 = p->mul2;
   e.ldo = (int)N;
   e.xcds = xcd_count();
+  e.s_col = p->s_col;
   e.lut = glut ? p->gelu_lut : nullptr;
   e.lut_bytes = glut ? (uint32_t)((8 * p->lut_n + 15) & ~15) : 0u;
   e.gk = GLutK{p->lut_k[0], p->lut_k[1], p->lut_k[2], p->lut_k[3], p->lut_k[4]};
@@ -192,12 +196,14 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   // a single-line table (lut_k[2] == 0: the L line is -inf) takes the epilogue without it
   const int epi_k = glut ? (p->lut_k[2] == 0.0f ? PG_GLUT1 : PG_GLUT) : epi;
   const bool s8 = epi == PG_QKV && p->bit_width == 8 && !b4 && !getenv("NQK_PG_NOS8");
-  const int key = pg_key(epi_k, K == 3072 ? 48 : (K == 192 ? 3 : 12), f32x, b4, s8, wm);
+  const int key = pg_key(epi_k, K == 3072 ? 48 : (K == 192 ? 3 : 12), f32x, b4, s8, wm, pc);
   const PgArgs x{a, bp, (int)M, (int)N, (int)lda, tiles_n, nt, nt < slots ? nt : slots, &e};
   // (A tail split — the rows of the whole rounds in one launch, the last round's row panels
   // in a second launch with one workgroup per tile — measured slower: FFN-down 142 -> 176 us,
   // out-proj 77 -> 90 us, profiles/r04_pg_split_dropped.txt)
-  if (!(pg_dispatch_i8(key, x) || pg_dispatch_resid(key, x) || pg_dispatch_tiny(key, x) || pg_dispatch_i4(key, x) ||
+  if (pc) {
+    if (!(pg_dispatch_pc(key, x) || pg_dispatch_pc4(key, x))) return 0;
+  } else if (!(pg_dispatch_i8(key, x) || pg_dispatch_resid(key, x) || pg_dispatch_tiny(key, x) || pg_dispatch_i4(key, x) ||
         pg_dispatch_wm2(key, x)))
     return 0;
   const int rc = launch_status("nqk_qgemm_fused(pg)");

@@ -204,6 +204,7 @@ struct PgEpi {
   GLutK gk;
   float blo, bhi;   // QKV: the clamp of v + 128 ([lo + 128, hi + 128] of the bit width)
   int xcds;         // XCDs of the device (the band count of the XCD-aware tile order)
+  const float* s_col;  // k_pg<PC>: per-column dequant scales [N] (nqk_epilogue.s_col) in sacc's place
 };
 
 // quantize (numpy_quantization.py:24-34) with f64 zero-point add and clipping
@@ -214,6 +215,7 @@ __device__ __forceinline__ int pg_quant_exact(float x, float s, double rs, doubl
   return (int)__builtin_rint(__builtin_fmin(__builtin_fmax(u, lo), hi));
 }
 
+constexpr float NQK_PG_QK1 = 0x1.9p-22f;   // 6.25 2^-24 per |v c1| (the QKV filter margin, below)
 // per-column-group constants of the exact fallback
 struct PgFix {
   float c1, k1, rsf, sacc, lim, s_out;
@@ -222,16 +224,23 @@ struct PgFix {
 // The rounding filter's exact fallback for element q of one epilogue step: recheck the
 // element's filter measure, and run the reference chain where it could not decide.
 // av: the int32 accumulators; xv: QKV the column bias, GELU h = RN(bias + RN(v sacc)).
-template <int EPI>
+// PC (QKV): sv holds the lane's 16 column scales; c1, k1 and the dequantize are the column's.
+template <int EPI, bool PC = false>
 __device__ __forceinline__ void pg_exact_fix1(int q, const int (&av)[16], const float (&xv)[16], uint32_t (&pk)[4],
-                                              const PgFix& f, const PgEpi& e) {
+                                              const PgFix& f, const PgEpi& e, const float (&sv)[16]) {
   const float vf = (float)av[q];
   const float x = xv[q];
+  float c1 = f.c1, k1 = f.k1, sacc = f.sacc;
+  if constexpr (PC && EPI == PG_QKV) {
+    sacc = sv[q];
+    c1 = sacc * f.rsf;
+    k1 = __builtin_fabsf(c1) * NQK_PG_QK1;
+  }
   bool slow;
   if constexpr (EPI == PG_QKV) {
-    const float u = __builtin_fmaf(vf, f.c1, x * f.rsf);
+    const float u = __builtin_fmaf(vf, c1, x * f.rsf);
     const float r = __builtin_rintf(u);
-    slow = !(__builtin_fmaf(__builtin_fabsf(vf), f.k1, __builtin_fabsf(u - r)) < f.lim);
+    slow = !(__builtin_fmaf(__builtin_fabsf(vf), k1, __builtin_fabsf(u - r)) < f.lim);
   } else {
     const float tf = gelu_fast(x) * f.rsf;
     const float r = __builtin_rintf(tf);
@@ -241,7 +250,7 @@ __device__ __forceinline__ void pg_exact_fix1(int q, const int (&av)[16], const 
     if (slow) {
       float y;
       if constexpr (EPI == PG_QKV) {
-        y = x + vf * f.sacc;  // F32X: the f64 dequantize, exactly
+        y = x + vf * sacc;  // F32X: the f64 dequantize, exactly
       } else {
         y = x;
         const float aa = ref_erf((float)((double)y * e.rdiv)) + e.add1;
@@ -259,21 +268,21 @@ __device__ __forceinline__ void pg_exact_fix1(int q, const int (&av)[16], const 
 // unrolled (its exact chain is short; measured faster, profiles/r03_pg_micro.txt).
 // gm (QKV and GELU): bit g set when some lane's filter measure of elements
 // 4 g .. 4 g + 3 failed; the other groups are skipped (their elements all passed)
-template <int EPI>
+template <int EPI, bool PC = false>
 __device__ __forceinline__ void pg_exact_fix(const int (&av)[16], const float (&xv)[16], uint32_t (&pk)[4],
-                                             const PgFix& f, const PgEpi& e, uint32_t gm = 15u) {
+                                             const PgFix& f, const PgEpi& e, const float (&sv)[16], uint32_t gm = 15u) {
   if constexpr (EPI == PG_QKV) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       if ((gm >> g) & 1u) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pg_exact_fix1<EPI>(4 * g + j, av, xv, pk, f, e);
+        for (int j = 0; j < 4; ++j) pg_exact_fix1<EPI, PC>(4 * g + j, av, xv, pk, f, e, sv);
       }
     }
   } else {
 #pragma clang loop unroll(disable)
     for (int q = 0; q < 16; ++q) {
-      if ((gm >> (q >> 2)) & 1u) pg_exact_fix1<EPI>(q, av, xv, pk, f, e);
+      if ((gm >> (q >> 2)) & 1u) pg_exact_fix1<EPI, false>(q, av, xv, pk, f, e, sv);  // GELU: h is in xv
     }
   }
 }
@@ -333,7 +342,6 @@ constexpr float PG_QLIM = 0x1.fffffcp-2f;
 // QKV filter margin (round 4): |u - t| <= 6 units (2^-24) of |v c1| + 5 of |c2| to first order —
 // the roundings of c1 = RN(sacc rsf), rsf = RN(1/s) and the fma on the fast side, of v sacc,
 // + bias and / s_out on the reference's — so 6.25 and 5.25 units (round 3 used 8 and 16)
-constexpr float NQK_PG_QK1 = 0x1.9p-22f;   // 6.25 2^-24 per |v c1|
 constexpr float NQK_PG_QKC2 = 0x1.5p-22f;  // 5.25 2^-24 per |c2|
 
 
@@ -346,7 +354,16 @@ constexpr float NQK_PG_QKC2 = 0x1.5p-22f;  // 5.25 2^-24 per |c2|
 // S8 (QKV with 8-bit outputs): v_cvt_pk_u8_f32 saturates to [0, 255] (tools/micro/cvtu8.hip:
 // every integral f32 in [-2^24, 2^24], profiles/r04_cvtu8.txt), which is then the clamp, so the
 // v_med3 before it goes.
-template <int EPI, int NK, bool F32X, bool B4, bool S8 = false, int WM = 1>
+// PC (QModel.per_channel): the dequant scale is the column's, e.s_col[n], in e.sacc[g]'s place.
+// The scales of a tile live in LDS, not in registers (16 more VGPRs per lane spilled the int8
+// QKV and GELU instances to scratch): a wave's 64 column terms ct[] of the tile are dead once the
+// wave has read its initial accumulators, so lanes 0..15 load the wave's 64 scales (a descriptor
+// of N floats: a wave past N reads zeros) and store them over its own ct[] words, right there at
+// the top of the tile (a compiler-visible load whose wait the compiler places before the store,
+// pinned in front of the k loop: the counted waits never see it in flight); the epilogue reads
+// them 4 at a time beside the bias.  QKV: c1[n] = RN32(s_col[n] rsf[g]) and
+// k1[n] = |c1[n]| NQK_PG_QK1 per element; the filter's error bound is per element and holds.
+template <int EPI, int NK, bool F32X, bool B4, bool S8 = false, int WM = 1, bool PC = false>
 __global__ void __launch_bounds__(256 * (WM == 2 ? 2 : 1), WM == 2 ? 1 : 2)
 k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, int lda, int tiles_n, int ntiles,
      PgEpi e) {
@@ -354,6 +371,7 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
   static_assert(NK % RD == 0 && (NK >= 2 * RD || NK == RD), "k_pg: NK a multiple of the ring depth");
   static_assert(RD == PG_RD || EPI != PG_RESID, "k_pg: the residual epilogue borrows ring slot 2 (3 stages)");
   static_assert(WM == 1 || WM == 2, "k_pg: one or two 128-row halves per tile");
+  static_assert(!PC || WM == 1, "k_pg: per-column scales overwrite a wave's own ct[] words (one wave per column quarter)");
   constexpr int WQ = WM == 2 ? 2 : 1;            // 4-wave groups per workgroup
   constexpr int APW = 2;                         // A LDS-DMA pieces per wave per stage
   constexpr int MS = 8;                          // 16-row subtiles of a wave
@@ -484,6 +502,7 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
     });
   };
 
+  const rsrc_t r_sc = pg_rsrc(PC ? e.s_col : nullptr, PC ? (uint32_t)((uint64_t)N * 4) : 0u);
   // ---------------------------------------------------------------- epilogue of a tile
   // rows r0 + 128 wm + 16 i + (l & 15), columns n0 + 64 wn + 16 (l >> 4) + 0..15
   auto epilogue = [&](const Src& s, int cslot) __attribute__((always_inline)) {
@@ -502,6 +521,8 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
 #pragma unroll
       for (int q = 0; q < 16; ++q) bias[q] = __int_as_float(bb[q >> 2][q & 3]);
     }
+    // PC: the scales of the lane's columns 4 g .. 4 g + 3, from the wave's ct[] words
+    auto sc4 = [&](int g) __attribute__((always_inline)) { return pg_lds16(cp + (64 * wn + 16 * lg + 4 * g) * 4); };
     {
       int g3 = 0;
       if constexpr (EPI == PG_QKV) {
@@ -566,7 +587,12 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
             const v4i& av4 = acc[i][q >> 2];
             // (packed: the unpacked form measured 146 -> 157 us, profiles/r04_glut_unpacked_dropped.txt)
             const v2f vf = v2f{(float)av4[q & 3], (float)av4[(q & 3) + 1]};
-            const v2f h = v2f{bias[q], bias[q + 1]} + vf * v2f{sacc, sacc};
+            v2f sq = v2f{sacc, sacc};
+            if constexpr (PC) {
+              const v4i s4 = sc4(q >> 2);
+              sq = v2f{__int_as_float(s4[q & 3]), __int_as_float(s4[(q & 3) + 1])};
+            }
+            const v2f h = v2f{bias[q], bias[q + 1]} + vf * sq;
             const v2f r = __builtin_elementwise_fma(h, v2f{e.gk.iwR, e.gk.iwR}, v2f{e.gk.cR, e.gk.cR});
             // PG_GLUT1: one line over both branches (the table's L line is -inf: max(R, L) = R)
             const v2f l = EPI == PG_GLUT1 ? r : __builtin_elementwise_fma(h, v2f{e.gk.iwL, e.gk.iwL}, v2f{e.gk.cL, e.gk.cL});
@@ -630,8 +656,14 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
           for (int q = 0; q < 16; q += 4) {
             const v4i& av4 = acc[i][q >> 2];
             const v2f vf0 = v2f{(float)av4[0], (float)av4[1]}, vf1 = v2f{(float)av4[2], (float)av4[3]};
-            const v2f h0 = v2f{bias[q], bias[q + 1]} + vf0 * v2f{sacc, sacc};
-            const v2f h1 = v2f{bias[q + 2], bias[q + 3]} + vf1 * v2f{sacc, sacc};
+            v2f sq0 = v2f{sacc, sacc}, sq1 = sq0;
+            if constexpr (PC) {
+              const v4i s4 = sc4(q >> 2);
+              sq0 = v2f{__int_as_float(s4[0]), __int_as_float(s4[1])};
+              sq1 = v2f{__int_as_float(s4[2]), __int_as_float(s4[3])};
+            }
+            const v2f h0 = v2f{bias[q], bias[q + 1]} + vf0 * sq0;
+            const v2f h1 = v2f{bias[q + 2], bias[q + 3]} + vf1 * sq1;
             hv[q] = h0[0];
             hv[q + 1] = h0[1];
             hv[q + 2] = h1[0];
@@ -660,16 +692,21 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
           for (int q = 0; q < 16 && (NQK_PG_DIAG & 2) == 0; q += 2) {
             // (pg_round2 measured slower here: a longer dependent chain)
             const v2f vf = v2f{(float)acc[i][q >> 2][q & 3], (float)acc[i][q >> 2][(q & 3) + 1]};
-            v2f dd, b;
+            v2f dd, b, c1q = v2f{c1, c1}, k1q = v2f{k1, k1};
+            if constexpr (PC) {  // the column's constants
+              const v4i s4 = sc4(q >> 2);
+              c1q = v2f{__int_as_float(s4[q & 3]) * rsf, __int_as_float(s4[(q & 3) + 1]) * rsf};
+              k1q = v2f{__builtin_fabsf(c1q[0]) * NQK_PG_QK1, __builtin_fabsf(c1q[1]) * NQK_PG_QK1};
+            }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-              const float u = __builtin_fmaf(vf[j], c1, c2[q + j]);
+              const float u = __builtin_fmaf(vf[j], c1q[j], c2[q + j]);
               const float rr = __builtin_rintf(u);
               dd[j] = u - rr;
               b[j] = rr + zp128;
             }
-            const float m0 = __builtin_fmaf(__builtin_fabsf(vf[0]), k1, __builtin_fabsf(dd[0]));
-            const float m1 = __builtin_fmaf(__builtin_fabsf(vf[1]), k1, __builtin_fabsf(dd[1]));
+            const float m0 = __builtin_fmaf(__builtin_fabsf(vf[0]), k1q[0], __builtin_fabsf(dd[0]));
+            const float m1 = __builtin_fmaf(__builtin_fabsf(vf[1]), k1q[1], __builtin_fabsf(dd[1]));
             pk[q >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(S8 ? b[0] : __builtin_amdgcn_fmed3f(b[0], e.blo, e.bhi), q & 3,
                                                         pk[q >> 2]);
             pk[q >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(S8 ? b[1] : __builtin_amdgcn_fmed3f(b[1], e.blo, e.bhi),
@@ -699,7 +736,16 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
 #pragma unroll
               for (int g = 0; g < 4; ++g) gm |= __any(wgr[g] >= __float_as_uint(lim)) ? 1u << g : 0u;
             }
-            pg_exact_fix<EPI>(av, xv, pk, PgFix{c1, k1, rsf, sacc, lim, s_out, rs_out, zp}, e, gm);
+            if constexpr (PC) {
+              float sv[16];
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                const v4i s4 = sc4(g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sv[4 * g + r] = __int_as_float(s4[r]);
+              }
+              pg_exact_fix<EPI, true>(av, xv, pk, PgFix{c1, k1, rsf, sacc, lim, s_out, rs_out, zp}, e, sv, gm);
+            } else pg_exact_fix<EPI>(av, xv, pk, PgFix{c1, k1, rsf, sacc, lim, s_out, rs_out, zp}, e, xv, gm);
           }
         }
         const v4u st = v4u{pk[0], pk[1], pk[2], pk[3]};
@@ -745,6 +791,12 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
     const v2f b23 = v2f{__int_as_float(bb[2]), __int_as_float(bb[3])};
     const rsrc_t r_out = pg_rsrc(e.out[0], s.tn * PG_BN + 64 * wn < N ? (uint32_t)((uint64_t)M * e.ldo * 4) : 0u);
     const float sacc = e.sacc[0];
+    float s4[4] = {sacc, sacc, sacc, sacc};  // PC: the scales of columns 4 a .. 4 a + 3
+    if constexpr (PC) {
+      const v4i sc = pg_lds16(cp + (64 * wn + 4 * ta) * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s4[r] = __int_as_float(sc[r]);
+    }
     sfor<0, 8>([&](auto I) __attribute__((always_inline)) {
       constexpr int i = decltype(I)::value;
       // this lane's 16 accumulators: row l15, columns 16 j + 4 lg + r (layout 1)
@@ -758,15 +810,15 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
       for (int k = 0; k < 4; ++k) {
         v4u st;
         if constexpr (F32X) {  // (unpacked: within noise, profiles/r04_qkv_nopk_ab.txt)
-          const v2f d01 = v2f{(float)t[k][0], (float)t[k][1]} * v2f{sacc, sacc};
-          const v2f d23 = v2f{(float)t[k][2], (float)t[k][3]} * v2f{sacc, sacc};
+          const v2f d01 = v2f{(float)t[k][0], (float)t[k][1]} * (PC ? v2f{s4[0], s4[1]} : v2f{sacc, sacc});
+          const v2f d23 = v2f{(float)t[k][2], (float)t[k][3]} * (PC ? v2f{s4[2], s4[3]} : v2f{sacc, sacc});
           const v2f y01 = (b01 + d01) + v2f{__uint_as_float(rv[k][0]), __uint_as_float(rv[k][1])};
           const v2f y23 = (b23 + d23) + v2f{__uint_as_float(rv[k][2]), __uint_as_float(rv[k][3])};
           st = v4u{__float_as_uint(y01[0]), __float_as_uint(y01[1]), __float_as_uint(y23[0]), __float_as_uint(y23[1])};
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float d = (float)((double)t[k][r] * (double)sacc);
+            const float d = (float)((double)t[k][r] * (double)(PC ? s4[r] : sacc));
             st[r] = __float_as_uint((__int_as_float(bb[r]) + d) + __uint_as_float(rv[k][r]));
           }
         }
@@ -823,6 +875,13 @@ k_pg(const int8_t* __restrict__ A, const int8_t* __restrict__ Bp, int M, int N, 
     pg_lgkm_tie(cinit[0], cinit[1], cinit[2], cinit[3]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) cinit[j] = B4 ? -(cinit[j] << 4) : -cinit[j];
+    if constexpr (PC) {  // the wave's 64 column scales over its own, now dead, ct[] words
+      if (lane < 16) {
+        const v4u sc = pg_load16(r_sc, (uint32_t)((cur.tn * PG_BN + 64 * wn + 4 * lane) * 4), 0u, 0);
+        *reinterpret_cast<v4u*>(lds + COLP + cs * 2048 + (64 * wn + 4 * lane) * 4) = sc;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     sfor<0, NK>([&](auto KT) __attribute__((always_inline)) {
       constexpr int kt = decltype(KT)::value;
       constexpr int slot = kt % RD;
@@ -914,12 +973,20 @@ bool pg_dispatch_resid(int key, const PgArgs& x);
 bool pg_dispatch_tiny(int key, const PgArgs& x);
 bool pg_dispatch_i4(int key, const PgArgs& x);
 bool pg_dispatch_wm2(int key, const PgArgs& x);
+bool pg_dispatch_pc(int key, const PgArgs& x);   // the per-column instances (PC), int8 weights
+bool pg_dispatch_pc4(int key, const PgArgs& x);  // ... nibble-packed weights
 
-// launch keys: EPI * 16 + (K 3072: 2, K 192: 1, else 0) * 4 + F32X + 2 B4 + 256 S8 + 512 WM2
-constexpr int pg_key(int epi, int nk, bool f32x, bool b4, bool s8, int wm) {
+// launch keys: EPI * 16 + (K 3072: 2, K 192: 1, else 0) * 4 + F32X + 2 B4 + 256 S8 + 512 WM2 + 1024 PC
+constexpr int pg_key(int epi, int nk, bool f32x, bool b4, bool s8, int wm, bool pc = false) {
   return epi * 16 + (nk == 48 ? 2 : (nk == 3 ? 1 : 0)) * 4 + (f32x ? 1 : 0) + (b4 ? 2 : 0) + (s8 ? 256 : 0) +
-         (wm == 2 ? 512 : 0);
+         (wm == 2 ? 512 : 0) + (pc ? 1024 : 0);
 }
+// a per-column instance (WM = 1)
+#define NQK_PG_CASE_PC(E, NKV, X, B, S)                                                                        \
+  case pg_key(E, NKV, X, B, S, 1, true):                                                                       \
+    hipLaunchKernelGGL((k_pg<E, NKV, X, B, S, 1, true>), dim3(x.grid), dim3(256), pg_lds_bytes(E, B, 1, NKV), stream(), \
+                       x.a, x.bp, x.m, x.n, x.lda, x.tiles_n, x.ntiles, *static_cast<const PgEpi*>(x.epi));    \
+    return true;
 #define NQK_PG_CASE(E, NKV, X, B, S, W)                                                                        \
   case pg_key(E, NKV, X, B, S, W):                                                                             \
     hipLaunchKernelGGL((k_pg<E, NKV, X, B, S, W>), dim3(x.grid), dim3(W == 2 ? 512 : 256), pg_lds_bytes(E, B, W, NKV), stream(), \

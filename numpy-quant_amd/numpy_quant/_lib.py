@@ -38,7 +38,8 @@ class Epilogue(ctypes.Structure):
                 ("gelu_lut", ctypes.c_void_p), ("lut_k", ctypes.c_float * 5), ("lut_n", ctypes.c_int32),
                 ("col_l1max", ctypes.c_int32),
                 ("ln_gamma", ctypes.c_void_p), ("ln_beta", ctypes.c_void_p), ("ln_out", ctypes.c_void_p),
-                ("ln_eps", ctypes.c_float), ("ln_scale", ctypes.c_float), ("ln_zp", ctypes.c_int64)]
+                ("ln_eps", ctypes.c_float), ("ln_scale", ctypes.c_float), ("ln_zp", ctypes.c_int64),
+                ("s_col", ctypes.c_void_p)]
 
 
 class Attention(ctypes.Structure):
@@ -85,6 +86,10 @@ SIGNATURES = {
     "nqk_quantize": [_p, _p, _i, _l, _f, _l, _i, _i, _p, _l],
     "nqk_dequantize": [_p, _i, _p, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp],
     "nqk_requantize": [_p, _i, _p, _i, _p, _i, _l, _l, _l, _f, _i, _l, _l, _l, _l, _p, _p, _lp, _f, _l, _i, _i],
+    "nqk_minmax_cols": [_p, _l, _l, _l, _p],
+    "nqk_quantize_cols": [_p, _p, _i, _l, _l, _p, _i],
+    "nqk_dequantize_cols": [_p, _i, _p, _l, _l, _l, _p, _i, _l, _l, _l, _l, _p, _p, _lp],
+    "nqk_requantize_cols": [_p, _i, _p, _i, _p, _i, _l, _l, _l, _p, _i, _l, _l, _l, _l, _p, _p, _lp, _f, _l, _i, _i],
     "nqk_image_lut": [_p, _p, _i, _p, _l, _l, _l, _l, _i],
     "nqk_image_resize_lut": [_p, _l, _p, _p, _l, _p, _i, _p, _l, _l, _l, _l],
     "nqk_rowsum": [_p, _i, _p, _l, _l, _l, _l, _l],

@@ -21,6 +21,12 @@ zp]}, "constants": [{"name", "dtype", "shape", "bit_width", "offset", "nbytes"}]
 1 = np.int64 scalar, 2 = 0-d int64 ndarray (the reference's quant_parameters returns
 each of these in some case, numpy_quantization.py:7-21; kept so reloaded parameters
 are the same Python objects as the calibrated ones).
+
+Version 2 (written only for a QModel with `per_channel` set; every other model keeps version 1
+and its bytes): the header has "per_channel": true, scale kind 2 is a float32 vector whose
+first entry is then the list of its bit patterns, and a constant that carries such a vector
+names its axis in "scale_axis" (-1 the last, 0 for a Gemm weight stored for transB).  Both
+versions load.
 """
 from __future__ import annotations
 
@@ -40,6 +46,10 @@ ALIGN = 256
 
 def _enc_qp(p) -> list:
     s = p.scale
+    if isinstance(s, np.ndarray) and s.ndim == 1:
+        if s.dtype != np.float32 or p.zero_point is not None:
+            raise ValueError("blob: a per-column scale is a float32 vector without a zero point")
+        return [[int(b) for b in np.ascontiguousarray(s).view(np.uint32)], 2, 0, 0]
     # the header keeps the reference's exact types (np.float32 scalar or 0-d f32 array):
     # anything else would come back narrowed to float32, a different Python object
     if not ((isinstance(s, np.floating) and s.dtype == np.float32) or
@@ -57,6 +67,8 @@ def _enc_qp(p) -> list:
 def _dec_qp(e):
     from .model import QuantizationParams
     bits, skind, zkind, zp = e
+    if skind == 2:
+        return QuantizationParams(np.array(bits, dtype=np.uint32).view(np.float32), None)
     f = np.uint32(bits).view(np.float32)
     scale = np.float32(f) if skind == 0 else np.array(f, dtype=np.float32)
     if zkind == 0:
@@ -90,12 +102,17 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
             _lib.call("nqk_memcpy_d2d", ctypes.c_void_p(payload.ptr + o), t.dev.vp, t.dev.nbytes)
         entries.append({"name": name, "dtype": t.dev.dtype.str, "shape": list(t.dev.shape),
                         "bit_width": int(t.bit_width), "offset": o, "nbytes": t.dev.nbytes})
-    header = {"version": 1, "bit_width": int(qmodel.bit_width),
+        if t.per_column:
+            entries[-1]["scale_axis"] = int(t.scale_axis)
+    per_channel = bool(getattr(qmodel, "per_channel", False))
+    header = {"version": 2 if per_channel else 1, "bit_width": int(qmodel.bit_width),
               "qparams": {k: _enc_qp(p) for k, p in qmodel.quant_params.items()},
               "constants": entries, "payload_bytes": off}
     if getattr(qmodel, "integer_conv", False):
         # written only when set: a model saved without the flag keeps its bytes (a missing key is False)
         header["integer_conv"] = True
+    if per_channel:
+        header["per_channel"] = True
     return header, payload
 
 
@@ -115,7 +132,7 @@ def constants_from(header: dict, payload: DeviceArray) -> Dict[str, "QTensor"]:
             raise ValueError(f"blob: bad extent for constant {e['name']}")
         view = DeviceArray(shape, dt, payload.block, payload.ptr + e["offset"])
         p = _dec_qp(qps[e["name"]])
-        t = QTensor(view, e["bit_width"], p.scale, p.zero_point)
+        t = QTensor(view, e["bit_width"], p.scale, p.zero_point, scale_axis=int(e.get("scale_axis", -1)))
         t._is_weight = True
         out[e["name"]] = t
     return out
@@ -129,12 +146,13 @@ def attach(model, header: dict, payload: DeviceArray):
     """The QModel of `model`'s graph with the blob's parameters and constants (the
     graph rewrite of Model.quantize, model.py:428-442, without calibration and without
     re-quantizing any constant)."""
-    if header.get("version") != 1:
+    if header.get("version") not in (1, 2):
         raise ValueError(f"unsupported blob version {header.get('version')}")
     qp = qparams_from(header)
     consts = constants_from(header, payload)
     return model._rewrite(header["bit_width"], lambda value, asym: qp[value.name], constants=consts,
-                          integer_conv=bool(header.get("integer_conv", False)))
+                          integer_conv=bool(header.get("integer_conv", False)),
+                          per_channel=bool(header.get("per_channel", False)), given=True)
 
 
 def encode_header(header: dict) -> bytes:

@@ -162,7 +162,7 @@ class Comparator:
         """Accumulate `got` (the quantized model's FTensor or QTensor) against `ref` (the float
         model's FTensor) under `name`: one call of the kernel, no synchronisation, no download.
         A QTensor is read in its integer storage when its zero point is a scalar or None; one
-        with a q_matmul zero-point term goes through `dequantize()` first, and one with a
+        with a q_matmul zero-point term or a per-column scale goes through `dequantize()` first, and one with a
         pending bias raises what `dequantize()` raises."""
         if not isinstance(ref, FTensor):
             raise ValueError(f"{name}: the reference side must be an FTensor (got {type(ref).__name__})")
@@ -173,8 +173,8 @@ class Comparator:
                              f"{tuple(got.dev.shape)})")
         scale = zp = None
         if isinstance(got, QTensor):
-            if got._bias is not None or isinstance(got._zero_point, K.ZpTerm):
-                y = got.dequantize().dev
+            if got._bias is not None or isinstance(got._zero_point, K.ZpTerm) or got.per_column:
+                y = got.dequantize().dev  # nqk_compare_stats takes one scalar scale
             else:
                 y, scale, zp = got.dev, got.scale, got._zero_point
         else:

@@ -142,6 +142,74 @@ def requantize(acc: DeviceArray, scale, zp, bias: DeviceArray | None, res_scale,
     return _narrow_if_fits(out, dt) if widen else out
 
 
+# ----------------------------------------------------------------------------- per-column scales
+def is_cols(scale) -> bool:
+    """Whether a scale is a per-column vector (QModel.per_channel) rather than a scalar."""
+    return np.ndim(scale) == 1
+
+
+def _check_cols(scale: DeviceArray, n: int, what: str) -> None:
+    if not isinstance(scale, DeviceArray) or scale.dtype != np.float32 or scale.shape != (n,):
+        raise ValueError(f"{what}: the scale vector must be a float32 DeviceArray [{n}]")
+
+
+def minmax_cols(x: DeviceArray) -> tuple[np.ndarray, np.ndarray]:
+    """(min, max) float32 [cols] of every column of a 2-D float32 array (nqk_minmax_cols)."""
+    if x.dtype != np.float32 or x.ndim != 2 or x.size == 0:
+        raise ValueError("minmax_cols expects a non-empty 2-D float32 array")
+    rows, cols = x.shape
+    res = DeviceArray((2, cols), np.float32)
+    _lib.call("nqk_minmax_cols", x.vp, rows, cols, cols, res.vp)
+    h = res.to_host()
+    return h[0], h[1]
+
+
+def quantize_cols(x: DeviceArray, bit_width: int, scale: DeviceArray, out_dtype=None) -> DeviceArray:
+    """numpy_quantization.py:24-34 without a zero point, the scale of column n = scale[n]
+    (nqk_quantize_cols).  Storage as `quantize` chooses it."""
+    if x.dtype != np.float32 or x.ndim < 1:
+        raise ValueError("quantize_cols expects a float32 array of at least one dimension")
+    cols = x.shape[-1]
+    _check_cols(scale, cols, "quantize_cols")
+    dt = np.dtype(out_dtype) if out_dtype is not None else storage_dtype(bit_width)
+    widen = out_dtype is None and _f32_bound_exceeds(bit_width, None)
+    q = DeviceArray(x.shape, np.int64 if widen else dt)
+    _lib.call("nqk_quantize_cols", x.vp, q.vp, q.code, x.size // cols if cols else 0, cols, scale.vp, int(bit_width))
+    return _narrow_if_fits(q, dt) if widen else q
+
+
+def dequantize_cols(q: DeviceArray, scale: DeviceArray, zp) -> DeviceArray:
+    """`dequantize` with scale[n] over the last axis (nqk_dequantize_cols)."""
+    if q.ndim < 1:
+        raise ValueError("dequantize_cols expects at least one dimension")
+    _check_cols(scale, q.shape[-1], "dequantize_cols")
+    out = DeviceArray(q.shape, np.float32)
+    flags, z, zpa, zpb, K, row, col, bmap = _zp_args(zp)
+    b, m, n = _bmn(q.shape) if q.ndim >= 2 else (1, 1, q.size)
+    _lib.call("nqk_dequantize_cols", q.vp, q.code, out.vp, b, m, n, scale.vp, flags, z, zpa, zpb, K, row, col, bmap)
+    return out
+
+
+def requantize_cols(acc: DeviceArray, scale: DeviceArray, zp, bias: DeviceArray | None, res_scale, res_zp,
+                    bit_width: int) -> DeviceArray:
+    """`requantize` with scale[n] over the last axis (nqk_requantize_cols)."""
+    if acc.ndim < 1:
+        raise ValueError("requantize_cols expects at least one dimension")
+    dt = storage_dtype(bit_width)
+    widen = _f32_bound_exceeds(bit_width, res_zp)
+    out = DeviceArray(acc.shape, np.int64 if widen else dt)
+    flags, z, zpa, zpb, K, row, col, bmap = _zp_args(zp)
+    b, m, n = _bmn(acc.shape) if acc.ndim >= 2 else (1, 1, acc.size)
+    _check_cols(scale, n, "requantize_cols")
+    if bias is not None and bias.size != n:
+        raise ValueError(f"bias of {bias.size} elements cannot broadcast over rows of {n}")
+    _lib.call("nqk_requantize_cols", acc.vp, acc.code, bias.vp if bias is not None else None,
+              bias.code if bias is not None else _lib.NQK_I64, out.vp, out.code, b, m, n, scale.vp,
+              flags, z, zpa, zpb, K, row, col, bmap, float(np.float32(res_scale)),
+              0 if res_zp is None else int(res_zp), 0 if res_zp is None else 1, int(bit_width))
+    return _narrow_if_fits(out, dt) if widen else out
+
+
 def rowsum(a: DeviceArray, batch: int, rows: int, k: int, ld: int, bstride: int) -> DeviceArray:
     out = DeviceArray((batch * rows,), np.int64)
     _lib.call("nqk_rowsum", a.vp, a.code, out.vp, batch, rows, k, ld, bstride)

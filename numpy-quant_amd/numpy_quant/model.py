@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from . import onnx_proto
-from .device import DeviceArray, sync
+from .device import DeviceArray, permute, sync
 from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
 from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, qconv2d, quantize_tensor, where)
@@ -239,6 +239,37 @@ def integer_conv_eligible(node) -> bool:
     return "pads" in a and "strides" in a
 
 
+def per_channel_axis(value):
+    """The axis of a constant's output columns when it may take one scale per column
+    (QModel.per_channel), else None.  Eligible: a 2-D float constant every consumer of which is a
+    MatMul that takes it as input 1 (columns on the last axis) or a Gemm that takes it as its
+    weight, input 1 (the last axis, axis 0 with transB), all naming the same axis."""
+    if not isinstance(value, Constant) or not isinstance(value.data, FTensor) or value.data.dev.ndim != 2:
+        return None
+    if not value.outputs or value.data.dev.size == 0:
+        return None
+    axes = set()
+    for node in value.outputs:
+        if node.op not in ("MatMul", "Gemm") or len(node.inputs) < 2 or node.inputs[1] is not value:
+            return None
+        if any(i is value for k, i in enumerate(node.inputs) if k != 1):
+            return None
+        axes.add(0 if node.op == "Gemm" and node.attrs.get("transB") else 1)
+    return axes.pop() if len(axes) == 1 else None
+
+
+def column_scales(tensor: FTensor, axis: int, bit_width: int) -> np.ndarray:
+    """float32 [N]: quant_parameters (numpy_quantization.py:7-21, symmetric) of every output
+    column's own range clamped to include 0 (tensor.py:304-308 applied to one column); the
+    columns lie on `axis` of the 2-D `tensor`.  The minima and maxima come from one kernel."""
+    dev = tensor.dev if axis % 2 == 1 else permute(tensor.dev, [1, 0])
+    mn, mx = K.minmax_cols(dev)
+    zero = np.array(0.0).astype(np.float32)
+    lo, hi = np.minimum(mn, zero), np.maximum(mx, zero)
+    return np.array([quant_parameters(lo[n], hi[n], bit_width, False)[0] for n in range(lo.shape[0])],
+                    dtype=np.float32)
+
+
 # ----------------------------------------------------------------------------- models
 class Model:
     def __init__(self, nodes: list[Node], values: list[Value], inputs: List[Variable], outputs: List[Variable]):
@@ -375,17 +406,18 @@ class Model:
                 vmin[val.name], vmax[val.name] = np.mean(flat.min()), np.mean(flat.max())
         return vmin, vmax
 
-    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False):
+    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
-        (QModel.integer_conv)."""
+        (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
+        MatMul / Gemm weight gets one scale per output column (QModel.per_channel)."""
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool):
             s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params, integer_conv=integer_conv)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -406,15 +438,21 @@ class Model:
             raise ValueError("calibrate_stream: no calibration batch")
         return cal.ranges()
 
-    def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False):
-        """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`."""
+    def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
+                        per_channel=False):
+        """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
+        `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
+        and maxima of the constants."""
+        if per_channel and clip_weights:
+            raise ValueError("quantize_stream: per_channel takes the exact per-column ranges of the weights; "
+                             "clip_weights does not combine with it")
         vmin, vmax = self.calibrate_stream(batches, percentile, clip_weights)
 
         def params(value: Value, asym: bool):
             s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params, integer_conv=integer_conv)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -471,11 +509,14 @@ class Model:
         states = cmp.states()
         return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
 
-    def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False):
+    def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False, per_channel=False):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
-        skipping the calibration forward."""
-        return self._rewrite(bit_width, lambda value, asym: quant_params[value.name], integer_conv=integer_conv)
+        skipping the calibration forward.  With `per_channel` the entry of an eligible weight
+        (per_channel_axis) may hold a float32 scale vector, one entry per output column; every
+        entry is taken as it is given."""
+        return self._rewrite(bit_width, lambda value, asym: quant_params[value.name], integer_conv=integer_conv,
+                             per_channel=per_channel, given=True)
 
     def load_quantized(self, path):
         """The QModel saved by `QModel.save(path)` (blob.py) on this model's graph:
@@ -483,9 +524,11 @@ class Model:
         from . import blob
         return blob.load(self, path)
 
-    def _rewrite(self, bit_width, params, constants=None, integer_conv=False):
+    def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
-        those constants are taken as they are instead of being quantized here."""
+        those constants are taken as they are instead of being quantized here.
+        `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
+        here from the weight's columns, or taken from `params` when `given`."""
         constants = constants or {}
         wanted = {}
         if constants:
@@ -504,10 +547,10 @@ class Model:
                 if want is not None and tuple(t.dev.shape) != want:
                     raise ValueError(f"blob constant {name}: shape {tuple(t.dev.shape)}, graph {want}")
 
-        def qconst(value, bw, scale, zp):
+        def qconst(value, bw, scale, zp, axis=-1):
             t = constants.get(value.name)
             if t is None:
-                return quantize_tensor(value.data, bw, scale, zp)
+                return quantize_tensor(value.data, bw, scale, zp, scale_axis=axis)
             wanted[value.name] = bw  # a bias is quantized at bw, then again at 4*bw: last wins
             return t
 
@@ -523,7 +566,25 @@ class Model:
         for value in self.values:
             if isinstance(value, Constant):
                 p = params(value, False)
-                qt = qconst(value, bit_width, p.scale, p.zero_point)
+                axis = per_channel_axis(value) if per_channel else None
+                if axis is not None and not given:
+                    p = QuantizationParams(column_scales(value.data, axis, bit_width), None)
+                if K.is_cols(p.scale):
+                    if not per_channel:
+                        raise ValueError(f"{value.name}: a scale vector is given, but per_channel is not set")
+                    if p.zero_point is not None:
+                        raise ValueError(f"{value.name}: a per-column scale has no zero point")
+                    if axis is None and not any(n.op == "Gemm" and len(n.inputs) > 2 and n.inputs[2] is value
+                                                for n in value.outputs):
+                        raise ValueError(f"{value.name}: a scale vector is given, but the constant is neither a "
+                                         "MatMul / Gemm weight nor a Gemm bias")
+                if K.is_cols(p.scale) and axis is None:
+                    # a Gemm bias with the vector a per_channel QModel's quant_params hold for it: the
+                    # Gemm branch below quantizes it at 4 * bit_width with s_x * s_w[n]; nothing to do here
+                    qvalues[value.name] = Constant(value.name, [], None)
+                    qp[value.name] = p
+                    continue
+                qt = qconst(value, bit_width, p.scale, p.zero_point, -1 if axis is None else axis)
                 qt._is_weight = True
                 qvalues[value.name] = Constant(value.name, [], qt)
                 qp[value.name] = p
@@ -539,7 +600,11 @@ class Model:
                         qvalues[iv.name] = Variable(iv.name, [], [], None)
                         qp[iv.name] = params(iv, True)
                 bias = node.inputs[2]
-                bscale = qp[node.inputs[0].name].scale * qp[node.inputs[1].name].scale
+                s_x, s_w = qp[node.inputs[0].name].scale, qp[node.inputs[1].name].scale
+                if K.is_cols(s_w):  # bscale[n] = s_x * s_w[n], float32 element by element
+                    bscale = (np.float32(s_x) * np.asarray(s_w, dtype=np.float32)).astype(np.float32)
+                else:
+                    bscale = s_x * s_w
                 qp[bias.name] = QuantizationParams(bscale, None)
                 qvalues[bias.name] = Constant(bias.name, [], qconst(bias, 4 * bit_width, bscale, None))
                 qnodes[node.name] = Node(node.name, "Gemm", node.attrs, [], [])
@@ -577,6 +642,7 @@ class Model:
         qmodel = QModel(list(qnodes.values()), list(qvalues.values()), qinputs, qoutputs, bit_width, qp)
         qmodel.image_preprocess = self.image_preprocess
         qmodel.integer_conv = bool(integer_conv)
+        qmodel.per_channel = bool(per_channel)
         return qmodel
 
 
@@ -598,6 +664,12 @@ class QModel(Model):
         # input) instead of dequantizing both for the float Conv.  Set it before the first call:
         # the fused plan reads it when it is compiled.
         self.integer_conv = False
+        # opt-in, not the reference's behaviour: every MatMul / Gemm weight was quantized with one
+        # scale per output column (per_channel_axis; tensor.QTensor carries the vector).  The
+        # integer products are unchanged; dequantize and requantize take the column's scale.  Set
+        # by Model.quantize(per_channel=True); the fused plan hands such a model's GEMMs the product
+        # vectors (nqk_epilogue.s_col): k_pg's per-column variant, or the small-tile GEMM kernel.
+        self.per_channel = False
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "

@@ -111,6 +111,12 @@ def _f32(x) -> float:
     return float(np.float32(x))
 
 
+def _sacc(s_a, s_w) -> float:
+    """f32(s_a) * f32(s_w) of a GEMM; of a per-column weight the first column's: no kernel reads
+    s_acc beside nqk_epilogue.s_col (the tests pass another column's scale there to hold that)"""
+    return _f32(np.float32(s_a) * np.float32(np.asarray(s_w).reshape(-1)[0]))
+
+
 def _zp(p) -> int:
     if p.zero_point is None:
         raise NoMatch("asymmetric parameters expected")
@@ -690,6 +696,9 @@ class FusedLayer:
     def __init__(self, qmodel, m: LayerMatch):
         self.m = m
         self.bw = qmodel.bit_width
+        # QModel.per_channel: every GEMM gets its per-column dequant scales (nqk_epilogue.s_col) and
+        # runs on k_pg's per-column variant, or on the small-tile kernel with the unpacked weights
+        self.pc = bool(getattr(qmodel, "per_channel", False))
         qp = qmodel.quant_params
         deq = qmodel._dequant_input
         cf = lambda v: _const_float(qmodel, v)  # noqa: E731
@@ -755,7 +764,22 @@ class FusedLayer:
         # reads its output (LN2 after the out-projection; the NEXT layer's LN1 after FFN-down, linked
         # by the Plan) runs inside its epilogue (nqk_epilogue.ln_out): 24 LayerNorm launches and their
         # f32 row reads fewer per forward.  NQK_NO_LNFUSE=1 keeps the separate launches.
-        self.ln_fuse = self.D == 192 and not os.environ.get("NQK_NO_LNFUSE")
+        self.ln_fuse = self.D == 192 and not os.environ.get("NQK_NO_LNFUSE") and not self.pc
+        # s_col[n] = f32(s_a) * f32(s_w[n]) per GEMM (for QKV the three weights' vectors, one after
+        # the other, under the common s_a); a weight that kept one scale fills its columns with it
+        self.scol = None
+        if self.pc:
+            def vec(p, s, n):
+                return np.broadcast_to((np.float32(p.scale) * np.asarray(s, np.float32)).astype(np.float32), (n,))
+            self.scol = {
+                "qkv": np.concatenate([vec(self.p_ln1, self.s_w[r], self.D) for r in "qkv"]),
+                "o": vec(self.p_ctx, self.s_wo, self.D), "1": vec(self.p_ln2, self.s_w1, self.F),
+                "2": vec(self.p_h, self.s_w2, self.D)}
+            self.scol = {k: DeviceArray.from_host(np.ascontiguousarray(v, dtype=np.float32))
+                         for k, v in self.scol.items()}
+            # no big-tile kernel takes s_col: keep of each nqk_pack_b image only its kind (2: the
+            # k_pg image is the nibble one)
+            self.bp = {k: None if v is None else (None, v[1]) for k, v in self.bp.items()}
         self.next_ln = None        # the next fused layer, whose LN1 this layer's FFN-down computes
         self.ln1_by_prev = False   # this layer's LN1 is computed by the previous layer's FFN-down
         # set by the Plan: the layer's output feeds only a LayerNorm whose Gather reads token 0, so
@@ -791,9 +815,16 @@ class FusedLayer:
     def _b(self, e, key, bt):
         """The B operand of a projection GEMM: its packed image if there is one (and the
         nqk_pack_pg image in e.bt_pg)."""
+        pg = self.bpg[key]
+        if self.pc:
+            # per-column scales: the unpacked bt (k_qgemm_epi's operand where k_pg declines the case);
+            # b_packed names the k_pg image's format only
+            e.s_col = self.scol[key].ptr
+            e.b_packed = 2 if pg is not None and self.bp[key] is not None and self.bp[key][1] == 2 else 0
+            e.bt_pg = None if pg is None else pg.ptr
+            return bt
         bp = self.bp[key]
         e.b_packed = 0 if bp is None else bp[1]
-        pg = self.bpg[key]
         e.bt_pg = None if pg is None else pg.ptr
         return bt if bp is None else bp[0]
 
@@ -914,7 +945,7 @@ class FusedLayer:
             s_a = np.float32(self.p_ln1.scale)
             e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln1), group_cols=D, col=self.col_qkv.ptr,
                           col_absmax=self.cmax["qkv"], col_l1max=self.l1max["qkv"], colterm=_ptr(self.ct["qkv"]),
-                          s_acc=[_f32(s_a * np.float32(self.s_w[r])) for r in "qkv"],
+                          s_acc=[_sacc(s_a, self.s_w[r]) for r in "qkv"],
                           s_out=[_f32(self.p_head[r].scale) for r in "qkv"],
                           zp_out=[_zp(self.p_head[r]) for r in "qkv"],
                           out=[q.ptr, k.ptr, v.ptr], bias=self.bias_qkv.ptr)
@@ -949,7 +980,7 @@ class FusedLayer:
         # 7) output projection + bias + residual
         e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ctx), col=self.col_o.ptr, col_absmax=self.cmax["o"], col_l1max=self.l1max["o"],
                       colterm=_ptr(self.ct["o"]),
-                      s_acc=[_f32(np.float32(self.p_ctx.scale) * np.float32(self.s_wo))], bias=self.bias_o.ptr,
+                      s_acc=[_sacc(self.p_ctx.scale, self.s_wo)], bias=self.bias_o.ptr,
                       resid=x.ptr, out=[x1.ptr])
         if ln_fuse:  # 8) LN2 + quantize inside the epilogue
             self._ln_into(e, self.g2, self.be2, self.eps2, self.p_ln2, ln2q)
@@ -959,7 +990,7 @@ class FusedLayer:
         # 9) FFN up + bias + GELU + quantize
         e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_ln2), col=self.col_1.ptr, col_absmax=self.cmax["1"], col_l1max=self.l1max["1"],
                       colterm=_ptr(self.ct["1"]),
-                      s_acc=[_f32(np.float32(self.p_ln2.scale) * np.float32(self.s_w1))], bias=self.bias_1.ptr,
+                      s_acc=[_sacc(self.p_ln2.scale, self.s_w1)], bias=self.bias_1.ptr,
                       s_out=[_f32(self.p_h.scale)], zp_out=[_zp(self.p_h)], out=[hh.ptr],
                       div=m.gelu_div, add1=m.gelu_add, mul2=m.gelu_mul)
         if self.glut is not None:
@@ -970,7 +1001,7 @@ class FusedLayer:
         # 10) FFN down + bias + residual
         e = self._epi(zp_flags=_lib.ZP_COL, zpa=_zp(self.p_h), col=self.col_2.ptr, col_absmax=self.cmax["2"], col_l1max=self.l1max["2"],
                       colterm=_ptr(self.ct["2"]),
-                      s_acc=[_f32(np.float32(self.p_h.scale) * np.float32(self.s_w2))], bias=self.bias_2.ptr,
+                      s_acc=[_sacc(self.p_h.scale, self.s_w2)], bias=self.bias_2.ptr,
                       resid=x1.ptr, out=[x2.ptr])
         nl = self.next_ln
         if nl is not None:  # the next layer's LN1 + quantize inside the epilogue, into the shared lnq rows

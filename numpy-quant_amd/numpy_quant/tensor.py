@@ -229,10 +229,15 @@ class FTensor:
 class QTensor:
     """Quantized tensor (tensor.py:227-293).  `dev` holds the integers in narrow
     storage; `zero_point` is None, an int64 scalar, or a ZpTerm (q_matmul output).
-    A pending Gemm bias (QTensor.__add__) is applied inside `requantize`."""
+    A pending Gemm bias (QTensor.__add__) is applied inside `requantize`.
+
+    `scale` may be a 1-D float32 vector (QModel.per_channel, not the reference's behaviour): one
+    scale per index of the last axis, or, for a 2-D weight kept as a Gemm with transB stores it
+    ([N][K]), of axis 0 (`scale_axis` = 0); its `.T` has the vector on the last axis again.
+    Such a tensor has no scalar zero point."""
 
     def __init__(self, data: Union[np.ndarray, DeviceArray], bit_width: int, scale: np.float32,
-                 zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None):
+                 zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None, scale_axis: int = -1):
         if isinstance(data, DeviceArray):
             if data.dtype.kind != "i":
                 raise ValueError("Use np.int64 for quantized tensors")
@@ -250,6 +255,22 @@ class QTensor:
                 raise ValueError("Use np.int64 for zero_point of quantized tensors")
             if zp.ndim:
                 raise ValueError("array zero points are only produced by q_matmul (ZpTerm)")
+        self.scale_axis = -1
+        self._pc = None  # per-column scale: device copies of the vectors, shared with .T
+        if K.is_cols(scale):
+            nd = self.dev.ndim
+            ax = int(scale_axis) % nd if nd else 0
+            if not isinstance(scale, np.ndarray) or scale.dtype != np.float32:
+                raise ValueError("Use a float32 ndarray for a per-column scale")
+            if nd == 0 or not (ax == nd - 1 or (nd == 2 and ax == 0)) or scale.shape[0] != self.dev.shape[ax]:
+                raise ValueError(f"per-column scale of {scale.shape[0]} entries on axis {scale_axis} of a tensor of "
+                                 f"shape {tuple(self.dev.shape)}: the last axis (or axis 0 of a matrix) expected")
+            if zero_point is not None and not isinstance(zero_point, K.ZpTerm):
+                raise ValueError("a per-column scale has no scalar zero point")
+            self.scale_axis = -1 if ax == nd - 1 else 0
+            self._pc = {}
+        elif np.ndim(scale) > 1:
+            raise ValueError("a scale is a scalar or a 1-D vector")
         self.bit_width = bit_width
         self.scale = scale
         self._zero_point = zero_point
@@ -284,30 +305,70 @@ class QTensor:
         return d
 
     @property
+    def per_column(self) -> bool:
+        return self._pc is not None
+
+    @property
+    def scale_dev(self) -> DeviceArray:
+        """The per-column scale vector on the device (uploaded once)."""
+        if self._pc is None:
+            raise ValueError("scale_dev: this tensor has a scalar scale")
+        d = self._pc.get("dev")
+        if d is None:
+            d = self._pc["dev"] = DeviceArray.from_host(np.ascontiguousarray(self.scale, dtype=np.float32))
+        return d
+
+    def _moved(self, dev: DeviceArray, perm=None, zero_point=None, bias=None) -> "QTensor":
+        """This tensor's parameters on `dev`, its axes permuted by `perm` (None: unchanged).  A
+        per-column scale follows its axis and refuses a place other than the last axis (or axis 0
+        of a matrix)."""
+        if self._pc is None:
+            return QTensor(dev, self.bit_width, self.scale, zero_point, bias)
+        nd = dev.ndim
+        if perm is not None:
+            ax = [int(q) % nd for q in perm].index(self.scale_axis % nd)
+        else:  # a reshape that kept the vector's axis (the caller checked)
+            ax = nd - 1 if self.scale_axis == -1 else 0
+        if not (ax == nd - 1 or (nd == 2 and ax == 0)):
+            raise ValueError("a per-column scale must stay on the last axis (or axis 0 of a matrix)")
+        out = QTensor(dev, self.bit_width, self.scale, zero_point, bias, scale_axis=ax)
+        out._pc = self._pc
+        return out
+
+    @property
     def T(self):
         if isinstance(self._zero_point, K.ZpTerm) or self._bias is not None:
             raise ValueError("transpose of a q_matmul output is not on the QModel path")
-        return QTensor(permute(self.dev, list(range(self.dev.ndim))[::-1]), self.bit_width, self.scale,
-                       self._zero_point)
+        perm = list(range(self.dev.ndim))[::-1]
+        return self._moved(permute(self.dev, perm), perm, self._zero_point)
 
     def reshape(self, shape: ITensor):
-        return QTensor(self.dev.reshape(_reshape_target(self.dev.shape, shape.data)), self.bit_width,
-                       self.scale, self._zero_point, self._bias)
+        tgt = _reshape_target(self.dev.shape, shape.data)
+        if self._pc is not None and (self.scale_axis != -1 or not tgt or tgt[-1] != self.dev.shape[-1]):
+            raise ValueError(f"reshape of a tensor with a per-column scale must keep its last axis "
+                             f"({tuple(self.dev.shape)} -> {tgt})")
+        return self._moved(self.dev.reshape(tgt), None, self._zero_point, self._bias)
 
     def transpose(self, *axes):
         perm = axes[0] if len(axes) == 1 and not isinstance(axes[0], int) else axes
-        return QTensor(permute(self.dev, list(perm)), self.bit_width, self.scale, self._zero_point)
+        if self._pc is not None and (isinstance(self._zero_point, K.ZpTerm) or self._bias is not None):
+            raise ValueError("transpose of a q_matmul output with a per-column scale is not supported")
+        return self._moved(permute(self.dev, list(perm)), list(perm), self._zero_point)
 
     def __add__(self, other: "QTensor"):
         if isinstance(other, QTensor):
             if self._bias is not None:
                 raise ValueError("only one pending bias is supported")
-            return QTensor(self.dev, self.bit_width, self.scale, self._zero_point, bias=other)
+            return self._moved(self.dev, None, self._zero_point, bias=other)
         raise ValueError(f"Cannot add QTensor with {other.__class__}")
 
     def dequantize(self):
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
+        if self._pc is not None:
+            if self.scale_axis == 0:  # a transB Gemm weight [N][K]: through its transpose
+                return FTensor(permute(self.T.dequantize().dev, [1, 0]))
+            return FTensor(K.dequantize_cols(self.dev, self.scale_dev, self._zero_point))
         return FTensor(K.dequantize(self.dev, self.scale, self._zero_point))
 
     def topk(self, k: int):
@@ -315,6 +376,8 @@ class QTensor:
         integer storage as it reads it."""
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
+        if self._pc is not None:  # the top-k kernel dequantizes with one scalar scale
+            return self.dequantize().topk(k)
         idx, prob, _ = K.topk_softmax(self.dev, k, scale=self.scale, zp=self._zero_point)
         return DeviceITensor(idx), FTensor(prob)
 
@@ -322,8 +385,13 @@ class QTensor:
         bias = None
         if self._bias is not None:
             bias = self._bias.dev
-        q = K.requantize(self.dev, self.scale, self._zero_point, bias, scale,
-                         None if zero_point is None else int(zero_point), bit_width)
+        rz = None if zero_point is None else int(zero_point)
+        if self._pc is not None:
+            if self.scale_axis != -1:
+                raise ValueError("requantize: the per-column scale must lie on the last axis")
+            q = K.requantize_cols(self.dev, self.scale_dev, self._zero_point, bias, scale, rz, bit_width)
+        else:
+            q = K.requantize(self.dev, self.scale, self._zero_point, bias, scale, rz, bit_width)
         return QTensor(q, bit_width, scale, zero_point)
 
     def weight_operand(self):
@@ -338,7 +406,21 @@ class QTensor:
         if other._bt is not None or getattr(other, "_is_weight", False):
             if other.dev.dtype == np.int8 and other.dev.ndim == 2:
                 bt, col = other.weight_operand()
+        if self._pc is not None:
+            raise ValueError("matmul: a per-column scale belongs to the right operand (the weight) only")
+        if other._pc is not None and other.scale_axis != -1:
+            raise ValueError("matmul: the weight's per-column scale must lie on its last axis (use .T)")
         acc, zt = K.qmatmul(self.dev, other.dev, self.zp_scalar, other.zp_scalar, bt, col)
+        if other._pc is not None:
+            # s[n] = f32(s_a) * f32(s_w[n]); the vector and its device copy are made once per s_a
+            key = ("out", np.float32(self.scale).tobytes())
+            hit = other._pc.get(key)
+            if hit is None:
+                vec = (np.float32(self.scale) * other.scale).astype(np.float32)
+                hit = other._pc[key] = (vec, {"dev": DeviceArray.from_host(vec)})
+            out = QTensor(acc, 4 * self.bit_width, hit[0], zt)
+            out._pc = hit[1]
+            return out
         scale = np.float32(self.scale) * np.float32(other.scale)
         return QTensor(acc, 4 * self.bit_width, scale, zt)
 
@@ -362,6 +444,8 @@ class QTensor:
         return QTensor(out, self.bit_width, self.scale, self._zero_point)
 
     def sigmoid(self):
+        if self._pc is not None:
+            raise ValueError("sigmoid of a tensor with a per-column scale is not supported")
         act = self.dequantize().sigmoid()
         return quantize_tensor(act, self.bit_width, self.scale, self.zero_point)
 
@@ -369,8 +453,26 @@ class QTensor:
 Tensor = Union[ITensor, FTensor, QTensor]
 
 
-def quantize_tensor(tensor: FTensor, bit_width: int, scale: np.float32, zero_point):
-    """tensor.py:299-301 on device."""
+def quantize_tensor(tensor: FTensor, bit_width: int, scale: np.float32, zero_point, scale_axis: int = -1):
+    """tensor.py:299-301 on device.  A 1-D float32 `scale` (QModel.per_channel) quantizes every
+    element with the scale of its index on the last axis, or on axis 0 of a matrix
+    (`scale_axis` = 0: a Gemm weight stored for transB); it takes no zero point."""
+    if K.is_cols(scale):
+        if zero_point is not None:
+            raise ValueError("a per-column scale takes no zero point")
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        sdev = DeviceArray.from_host(scale)
+        nd = tensor.dev.ndim
+        ax = int(scale_axis) % nd if nd else 0
+        if nd == 2 and ax == 0:
+            q = permute(K.quantize_cols(permute(tensor.dev, [1, 0]), bit_width, sdev), [1, 0])
+        elif nd and ax == nd - 1:
+            q = K.quantize_cols(tensor.dev, bit_width, sdev)
+        else:
+            raise ValueError("a per-column scale lies on the last axis, or on axis 0 of a matrix")
+        out = QTensor(q, bit_width, scale=scale, zero_point=None, scale_axis=ax)
+        out._pc["dev"] = sdev
+        return out
     q, _ = K.quantize(tensor.dev, bit_width, scale, None if zero_point is None else int(zero_point))
     return QTensor(q, bit_width, scale=scale, zero_point=zero_point)
 
