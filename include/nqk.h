@@ -468,6 +468,16 @@ typedef struct nqk_epilogue {
    * nqk_pack_pg4 nibble image, 0 as nqk_pack_pg's), the small-tile kernel from bt otherwise
    * (nqk_qgemm_last_kernel() says which).  ln_out, or b_packed = 1, beside s_col is refused. */
   const float* s_col;
+  /* The weights' own bit width (opt-in: QModel.weight_bit_width), or 0: nothing is stated and
+   * every call behaves as before the field existed.  w_bits = w, 1 <= w <= 8, states that every
+   * value of bt / bt_pg lies in [-2^(w-1), 2^(w-1) - 1]; bit_width stays the width of the OUTPUT
+   * activation (the epilogue's clamps) and says nothing about the weights.  With b_packed = 2 it
+   * replaces the nibble image's condition bit_width <= 4 by w_bits <= 4: 8-bit activations then run
+   * on the nibble-packed weights (W4A8).  k_pg takes such a call when
+   * 16 (128 col_l1max + col_absmax |zpa|) < 2^31 (its MFMAs sum 16 a w from 16 x the column term;
+   * col_l1max and col_absmax must both be given), QKV with bit_width = 8 on the saturating-store
+   * instance.  b_packed = 2 beside w_bits > 4 is refused. */
+  int32_t w_bits;
 } nqk_epilogue;
 /* int8 MFMA GEMM C = A . Bt^T (layouts as nqk_qgemm_i8) with a fused epilogue:
  *   QKV    model.py MatMul -> Add(bias) -> Reshape -> Transpose -> quantize, 3 groups
@@ -481,7 +491,7 @@ typedef struct nqk_epilogue {
  * operand is read as whole 128-byte lines (replaces no reference function: a layout of
  * the same numpy_quantization.py:44-61 q_matmul operand). */
 int nqk_pack_b(const int8_t* bt, int8_t* out, int64_t N, int64_t K, int64_t ldb);
-/* int4 weights (every value in [-8, 7], bit width <= 4): the same tiles nibble-packed,
+/* int4 weights (every value in [-8, 7]: the weights' bit width <= 4): the same tiles nibble-packed,
  * ceil(N/256)*256*K/2 bytes; the GEMM unpacks them in registers after the LDS stage
  * (b_packed = 2).  BASELINE configs[4] ("int4 packed weights"). */
 int nqk_pack_b4(const int8_t* bt, uint8_t* out, int64_t N, int64_t K, int64_t ldb);
@@ -493,7 +503,7 @@ int nqk_pack_b4(const int8_t* bt, uint8_t* out, int64_t N, int64_t K, int64_t ld
  * residual epilogues, f32 outputs); ceil(N/256)*256*K bytes (a layout of the
  * numpy_quantization.py:44-61 q_matmul operand, replaces no reference function). */
 int nqk_pack_pg(const int8_t* bt, int8_t* out, int64_t N, int64_t K, int64_t ldb, int layout);
-/* int4 weights (every value in [-8, 7], bit width <= 4): the same stages nibble-packed, 256 rows
+/* int4 weights (every value in [-8, 7]: the weights' bit width <= 4, whatever the activations'): the same stages nibble-packed, 256 rows
  * x 32 bytes each, ceil(N/256)*256*K/2 bytes; k_pg unpacks them in registers after the LDS stage
  * (nqk_epilogue.b_packed = 2 with bt_pg = this image).  BASELINE configs[4]. */
 int nqk_pack_pg4(const int8_t* bt, uint8_t* out, int64_t N, int64_t K, int64_t ldb, int layout);

@@ -1974,6 +1974,9 @@ extern "C" int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64
   bool scales_ok = normal(params->s_out[0]) || epi == EPI_RESID || epi == EPI_NULL;
   if (epi == EPI_QKV) scales_ok = normal(params->s_out[0]) && normal(params->s_out[1]) && normal(params->s_out[2]);
   if (epi == EPI_GELU) scales_ok = scales_ok && normal(params->div);
+  if (params->w_bits < 0 || params->w_bits > 8) return fail("nqk_qgemm_fused: w_bits is 0 (not stated) or the weights' width, 1..8");
+  if (params->b_packed == 2 && params->w_bits > 4)
+    return fail("nqk_qgemm_fused: a nibble image (b_packed = 2) holds weights of at most 4 bits (w_bits)");
   if (params->b_packed == 2 && (!i32 || epi == EPI_NULL))
     return fail("nqk_qgemm_fused: int4 packed weights need the int32 zero-point algebra");
   if (params->ln_out != nullptr) {

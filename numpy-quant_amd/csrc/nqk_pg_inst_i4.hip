@@ -5,6 +5,7 @@
 namespace nqk {
 bool pg_dispatch_i4(int key, const PgArgs& x) {
   switch (key) {
+    NQK_PG_CASE(PG_QKV, 12, true, true, true, 1)  // 8-bit outputs (nqk_epilogue.w_bits): the saturating store
     NQK_PG_CASE(PG_QKV, 12, true, true, false, 1)
     NQK_PG_CASE(PG_GELU, 12, true, true, false, 1)
     NQK_PG_CASE(PG_GLUT, 12, true, true, false, 1)

@@ -5,6 +5,7 @@
 namespace nqk {
 bool pg_dispatch_pc4(int key, const PgArgs& x) {
   switch (key) {
+    NQK_PG_CASE_PC(PG_QKV, 12, true, true, true)  // 8-bit outputs (nqk_epilogue.w_bits): the saturating store
     NQK_PG_CASE_PC(PG_QKV, 12, true, true, false)
     NQK_PG_CASE_PC(PG_GELU, 12, true, true, false)
     NQK_PG_CASE_PC(PG_GLUT, 12, true, true, false)

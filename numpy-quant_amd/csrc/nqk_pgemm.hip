@@ -93,7 +93,15 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   if (bp == nullptr || p->colterm == nullptr) return 0;
   // b_packed == 2: int4 weights; bp is then the nqk_pack_pg4 nibble image (k_pg<B4>)
   const bool b4 = p->b_packed == 2;
-  if (b4 && !(p->bit_width <= 4 && p->col_absmax > 0 && 16.0 * (double)p->col_absmax * (double)llabs(p->zpa) < 2147483647.0))
+  if (b4 && p->w_bits == 0 &&
+      !(p->bit_width <= 4 && p->col_absmax > 0 && 16.0 * (double)p->col_absmax * (double)llabs(p->zpa) < 2147483647.0))
+    return 0;
+  // w_bits: the weights' own width, whatever the activations' (W4A8).  The MFMAs sum 16 a w from
+  // the initial accumulator -16 colterm, |a| <= 128: every partial sum stays below
+  // 16 (128 col_l1max + col_absmax |zpa|), which must fit int32
+  if (b4 && p->w_bits != 0 &&
+      !(p->w_bits >= 1 && p->w_bits <= 4 && p->col_absmax > 0 && p->col_l1max > 0 &&
+        16.0 * (128.0 * (double)p->col_l1max + (double)p->col_absmax * (double)llabs(p->zpa)) < 2147483648.0))
     return 0;
   if (!(epi == PG_QKV || epi == PG_RESID || epi == PG_GELU)) return 0;
   // per-column dequant scales (nqk_epilogue.s_col): the PC instances (WM = 1)
@@ -195,7 +203,8 @@ int pg_launch(int epi, const int8_t* a, const int8_t* bp, int64_t M, int64_t N, 
   const int slots = (wm == 2 ? 1 : 2) * pg_num_cus();
   // a single-line table (lut_k[2] == 0: the L line is -inf) takes the epilogue without it
   const int epi_k = glut ? (p->lut_k[2] == 0.0f ? PG_GLUT1 : PG_GLUT) : epi;
-  const bool s8 = epi == PG_QKV && p->bit_width == 8 && !b4 && !getenv("NQK_PG_NOS8");
+  // (nibble weights: the S8 instances exist for 8-bit outputs, which only a stated w_bits brings)
+  const bool s8 = epi == PG_QKV && p->bit_width == 8 && (!b4 || p->w_bits != 0) && !getenv("NQK_PG_NOS8");
   const int key = pg_key(epi_k, K == 3072 ? 48 : (K == 192 ? 3 : 12), f32x, b4, s8, wm, pc);
   const PgArgs x{a, bp, (int)M, (int)N, (int)lda, tiles_n, nt, nt < slots ? nt : slots, &e};
   // (A tail split — the rows of the whole rounds in one launch, the last round's row panels

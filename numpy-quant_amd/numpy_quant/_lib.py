@@ -39,7 +39,7 @@ class Epilogue(ctypes.Structure):
                 ("col_l1max", ctypes.c_int32),
                 ("ln_gamma", ctypes.c_void_p), ("ln_beta", ctypes.c_void_p), ("ln_out", ctypes.c_void_p),
                 ("ln_eps", ctypes.c_float), ("ln_scale", ctypes.c_float), ("ln_zp", ctypes.c_int64),
-                ("s_col", ctypes.c_void_p)]
+                ("s_col", ctypes.c_void_p), ("w_bits", ctypes.c_int32)]
 
 
 class Attention(ctypes.Structure):

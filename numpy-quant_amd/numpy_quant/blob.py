@@ -25,8 +25,12 @@ are the same Python objects as the calibrated ones).
 Version 2 (written only for a QModel with `per_channel` set; every other model keeps version 1
 and its bytes): the header has "per_channel": true, scale kind 2 is a float32 vector whose
 first entry is then the list of its bit patterns, and a constant that carries such a vector
-names its axis in "scale_axis" (-1 the last, 0 for a Gemm weight stored for transB).  Both
-versions load.
+names its axis in "scale_axis" (-1 the last, 0 for a Gemm weight stored for transB).
+
+Version 3 (written only for a QModel whose `weight_bit_width` differs from its `bit_width`; every
+other model keeps version 1 or 2 and its bytes): version 2's header with "weight_bit_width": w,
+and "per_channel" as the model has it.  The constants' own "bit_width" entries already say which
+width each holds.  All three versions load.
 """
 from __future__ import annotations
 
@@ -105,7 +109,9 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
         if t.per_column:
             entries[-1]["scale_axis"] = int(t.scale_axis)
     per_channel = bool(getattr(qmodel, "per_channel", False))
-    header = {"version": 2 if per_channel else 1, "bit_width": int(qmodel.bit_width),
+    wbw = int(getattr(qmodel, "weight_bit_width", qmodel.bit_width))
+    mixed = wbw != int(qmodel.bit_width)
+    header = {"version": 3 if mixed else (2 if per_channel else 1), "bit_width": int(qmodel.bit_width),
               "qparams": {k: _enc_qp(p) for k, p in qmodel.quant_params.items()},
               "constants": entries, "payload_bytes": off}
     if getattr(qmodel, "integer_conv", False):
@@ -113,6 +119,8 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
         header["integer_conv"] = True
     if per_channel:
         header["per_channel"] = True
+    if mixed:
+        header["weight_bit_width"] = wbw
     return header, payload
 
 
@@ -146,13 +154,14 @@ def attach(model, header: dict, payload: DeviceArray):
     """The QModel of `model`'s graph with the blob's parameters and constants (the
     graph rewrite of Model.quantize, model.py:428-442, without calibration and without
     re-quantizing any constant)."""
-    if header.get("version") not in (1, 2):
+    if header.get("version") not in (1, 2, 3):
         raise ValueError(f"unsupported blob version {header.get('version')}")
     qp = qparams_from(header)
     consts = constants_from(header, payload)
-    return model._rewrite(header["bit_width"], lambda value, asym: qp[value.name], constants=consts,
+    return model._rewrite(header["bit_width"], lambda value, asym, bw=None: qp[value.name], constants=consts,
                           integer_conv=bool(header.get("integer_conv", False)),
-                          per_channel=bool(header.get("per_channel", False)), given=True)
+                          per_channel=bool(header.get("per_channel", False)), given=True,
+                          weight_bit_width=header.get("weight_bit_width"))
 
 
 def encode_header(header: dict) -> bytes:

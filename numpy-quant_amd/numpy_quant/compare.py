@@ -310,11 +310,15 @@ def _reiterable(batches, what: str):
         raise ValueError(f"sweep: {what} is a one-pass iterator; pass a list (it is read once per bit width)")
 
 
-def sweep(model, calibration_batches, eval_batches, bit_widths=(8, 6, 4), percentile=100.0, **compare_kw) -> dict:
+def sweep(model, calibration_batches, eval_batches, bit_widths=(8, 6, 4), percentile=100.0, weight_bit_widths=None,
+          **compare_kw) -> dict:
     """{bit_width: Report}: per bit width `model.quantize_stream(calibration_batches, bit_width,
     percentile)` followed by `model.compare(qmodel, eval_batches, **compare_kw)`.  Both batch
     arguments are read once per bit width, so they must be re-iterable (a list, not a
-    generator); `labels` among compare_kw likewise."""
+    generator); `labels` among compare_kw likewise.
+    With `weight_bit_widths` (a sequence) the sweep runs over the pairs (activation width a of
+    `bit_widths`, weight width w of `weight_bit_widths`) that Model.quantize defines, w <= a, in
+    that order, and returns {(a, w): Report}; no such pair at all is an error."""
     _reiterable(calibration_batches, "calibration_batches")
     _reiterable(eval_batches, "eval_batches")
     if compare_kw.get("labels") is not None:
@@ -322,10 +326,19 @@ def sweep(model, calibration_batches, eval_batches, bit_widths=(8, 6, 4), percen
     widths = list(bit_widths)
     if not widths:
         raise ValueError("sweep: no bit width")
-    for bw in widths:
+    wwidths = None if weight_bit_widths is None else list(weight_bit_widths)
+    for bw in widths + (wwidths or []):
         if isinstance(bw, bool) or not isinstance(bw, (int, np.integer)) or not 1 <= int(bw) <= 16:
             raise ValueError(f"sweep: bit widths are integers in 1..16 (got {bw!r})")
     out = {}
+    if wwidths is not None:
+        pairs = [(int(a), int(w)) for a in widths for w in wwidths if int(w) <= int(a)]
+        if not pairs:
+            raise ValueError("sweep: no (bit width, weight bit width) pair with weight bit width <= bit width")
+        for a, w in pairs:
+            qmodel = model.quantize_stream(calibration_batches, bit_width=a, percentile=percentile, weight_bit_width=w)
+            out[(a, w)] = model.compare(qmodel, eval_batches, **compare_kw)
+        return out
     for bw in widths:
         qmodel = model.quantize_stream(calibration_batches, bit_width=int(bw), percentile=percentile)
         out[int(bw)] = model.compare(qmodel, eval_batches, **compare_kw)

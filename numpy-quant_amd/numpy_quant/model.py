@@ -270,6 +270,19 @@ def column_scales(tensor: FTensor, axis: int, bit_width: int) -> np.ndarray:
                     dtype=np.float32)
 
 
+def weight_width(bit_width, weight_bit_width) -> int:
+    """The width of the eligible weights (per_channel_axis) of a model quantized at `bit_width`:
+    `weight_bit_width`, an int with 1 <= weight_bit_width <= bit_width, or bit_width for None.
+    Anything else raises ValueError."""
+    if weight_bit_width is None:
+        return bit_width
+    if (isinstance(weight_bit_width, bool) or not isinstance(weight_bit_width, (int, np.integer))
+            or not 1 <= weight_bit_width <= bit_width):
+        raise ValueError(f"weight_bit_width must be an integer in 1..bit_width ({bit_width}), or None "
+                         f"(got {weight_bit_width!r})")
+    return int(weight_bit_width)
+
+
 # ----------------------------------------------------------------------------- models
 class Model:
     def __init__(self, nodes: list[Node], values: list[Value], inputs: List[Variable], outputs: List[Variable]):
@@ -406,18 +419,23 @@ class Model:
                 vmin[val.name], vmax[val.name] = np.mean(flat.min()), np.mean(flat.max())
         return vmin, vmax
 
-    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False):
+    def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
+                 weight_bit_width=None):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
         (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
-        MatMul / Gemm weight gets one scale per output column (QModel.per_channel)."""
+        MatMul / Gemm weight gets one scale per output column (QModel.per_channel).
+        `weight_bit_width=w` (not the reference's behaviour either, 1 <= w <= bit_width): the same
+        weights are quantized at w bits, everything else at bit_width (QModel.weight_bit_width)."""
+        weight_width(bit_width, weight_bit_width)  # refused before the calibration forward
         vmin, vmax = self.calibrate(calibration_inputs)
 
-        def params(value: Value, asym: bool):
-            s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
+        def params(value: Value, asym: bool, bw=bit_width):
+            s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bw, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
+                             weight_bit_width=weight_bit_width)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -439,20 +457,22 @@ class Model:
         return cal.ranges()
 
     def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
-                        per_channel=False):
+                        per_channel=False, weight_bit_width=None):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
         `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
         and maxima of the constants."""
+        weight_width(bit_width, weight_bit_width)
         if per_channel and clip_weights:
             raise ValueError("quantize_stream: per_channel takes the exact per-column ranges of the weights; "
                              "clip_weights does not combine with it")
         vmin, vmax = self.calibrate_stream(batches, percentile, clip_weights)
 
-        def params(value: Value, asym: bool):
-            s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bit_width, asymmetric=asym)
+        def params(value: Value, asym: bool, bw=bit_width):
+            s, z = quant_parameters(vmin[value.name], vmax[value.name], bit_width=bw, asymmetric=asym)
             return QuantizationParams(s, z)
 
-        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel)
+        return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
+                             weight_bit_width=weight_bit_width)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -509,14 +529,17 @@ class Model:
         states = cmp.states()
         return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
 
-    def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False, per_channel=False):
+    def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False, per_channel=False,
+                      weight_bit_width=None):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
         skipping the calibration forward.  With `per_channel` the entry of an eligible weight
         (per_channel_axis) may hold a float32 scale vector, one entry per output column; every
-        entry is taken as it is given."""
-        return self._rewrite(bit_width, lambda value, asym: quant_params[value.name], integer_conv=integer_conv,
-                             per_channel=per_channel, given=True)
+        entry is taken as it is given.  With `weight_bit_width` the entry of an eligible weight is
+        the scale of that width: the weight is quantized with it at weight_bit_width."""
+        return self._rewrite(bit_width, lambda value, asym, bw=None: quant_params[value.name],
+                             integer_conv=integer_conv, per_channel=per_channel, given=True,
+                             weight_bit_width=weight_bit_width)
 
     def load_quantized(self, path):
         """The QModel saved by `QModel.save(path)` (blob.py) on this model's graph:
@@ -524,11 +547,17 @@ class Model:
         from . import blob
         return blob.load(self, path)
 
-    def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False):
+    def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False,
+                 weight_bit_width=None):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here.
         `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
-        here from the weight's columns, or taken from `params` when `given`."""
+        here from the weight's columns, or taken from `params` when `given`.
+        `weight_bit_width`: the width of the same eligible weights (range, scale and integers, per
+        tensor or per column); every other constant, every activation and every bias (4 * bit_width)
+        keeps `bit_width`.  `params(value, asym, bw)` then gives an eligible weight's parameters at
+        that width."""
+        wbw = weight_width(bit_width, weight_bit_width)
         constants = constants or {}
         wanted = {}
         if constants:
@@ -565,10 +594,12 @@ class Model:
             qp[value.name] = params(value, isinstance(value, Variable))
         for value in self.values:
             if isinstance(value, Constant):
-                p = params(value, False)
+                # the constant's width: the weights' for a MatMul / Gemm weight, else the model's
+                cbw = wbw if wbw != bit_width and per_channel_axis(value) is not None else bit_width
+                p = params(value, False) if cbw == bit_width else params(value, False, cbw)
                 axis = per_channel_axis(value) if per_channel else None
                 if axis is not None and not given:
-                    p = QuantizationParams(column_scales(value.data, axis, bit_width), None)
+                    p = QuantizationParams(column_scales(value.data, axis, cbw), None)
                 if K.is_cols(p.scale):
                     if not per_channel:
                         raise ValueError(f"{value.name}: a scale vector is given, but per_channel is not set")
@@ -584,7 +615,7 @@ class Model:
                     qvalues[value.name] = Constant(value.name, [], None)
                     qp[value.name] = p
                     continue
-                qt = qconst(value, bit_width, p.scale, p.zero_point, -1 if axis is None else axis)
+                qt = qconst(value, cbw, p.scale, p.zero_point, -1 if axis is None else axis)
                 qt._is_weight = True
                 qvalues[value.name] = Constant(value.name, [], qt)
                 qp[value.name] = p
@@ -643,6 +674,7 @@ class Model:
         qmodel.image_preprocess = self.image_preprocess
         qmodel.integer_conv = bool(integer_conv)
         qmodel.per_channel = bool(per_channel)
+        qmodel.weight_bit_width = wbw
         return qmodel
 
 
@@ -670,6 +702,13 @@ class QModel(Model):
         # by Model.quantize(per_channel=True); the fused plan hands such a model's GEMMs the product
         # vectors (nqk_epilogue.s_col): k_pg's per-column variant, or the small-tile GEMM kernel.
         self.per_channel = False
+        # opt-in, not the reference's behaviour: the width of every MatMul / Gemm weight (the
+        # constants per_channel_axis names), 1 <= weight_bit_width <= bit_width; activations, every
+        # other constant and the biases (4 * bit_width) keep bit_width.  Equal to bit_width unless
+        # Model.quantize(weight_bit_width=...) set it.  The integer products are q_matmul's; at
+        # weight_bit_width <= 4 the fused plan packs the weights as nibbles under activations of any
+        # width up to 8 (nqk_epilogue.w_bits).
+        self.weight_bit_width = bit_width
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "

@@ -696,6 +696,10 @@ class FusedLayer:
     def __init__(self, qmodel, m: LayerMatch):
         self.m = m
         self.bw = qmodel.bit_width
+        # QModel.weight_bit_width: the four weights' own width; it alone chooses their packing
+        # (nibbles at <= 4 bits), and the GEMMs are told it (nqk_epilogue.w_bits) where it differs
+        # from the activations' width, which stays the epilogues' output width
+        self.wbw = int(getattr(qmodel, "weight_bit_width", self.bw))
         # QModel.per_channel: every GEMM gets its per-column dequant scales (nqk_epilogue.s_col) and
         # runs on k_pg's per-column variant, or on the small-tile kernel with the unpacked weights
         self.pc = bool(getattr(qmodel, "per_channel", False))
@@ -732,11 +736,11 @@ class FusedLayer:
         self.F = self.bt_1.shape[0]
         # tile-packed weight images (whole 128-B lines per LDS-DMA piece), when the big-tile
         # GEMM takes the shape
-        self.bp = {k: _pack_b(b, self.bw) for k, b in (("qkv", self.bt_qkv), ("o", self.bt_o), ("1", self.bt_1),
+        self.bp = {k: _pack_b(b, self.wbw) for k, b in (("qkv", self.bt_qkv), ("o", self.bt_o), ("1", self.bt_1),
                                                         ("2", self.bt_2))}
         # the persistent 16x16x64 GEMM's weight images (nqk_pack_pg; used where it takes the case)
         # (int4 weights: the nibble image, paired with the big-tile GEMM's nibble pack: b_packed 2)
-        self.bpg = {k: _pack_pg(b, self.bw, lay, nibbles=self.bp[k] is not None and self.bp[k][1] == 2)
+        self.bpg = {k: _pack_pg(b, self.wbw, lay, nibbles=self.bp[k] is not None and self.bp[k][1] == 2)
                     for k, b, lay in (("qkv", self.bt_qkv, 0), ("o", self.bt_o, 1), ("1", self.bt_1, 0),
                                       ("2", self.bt_2, 1))}
         # max |column sum| of each weight: lets the GEMM epilogues prove f32 exactness
@@ -793,6 +797,7 @@ class FusedLayer:
     def _epi(self, **kw) -> Epilogue:
         e = Epilogue()
         e.bit_width = self.bw
+        e.w_bits = self.wbw if self.wbw != self.bw else 0
         e.group_cols = kw.pop("group_cols", 1 << 30)
         e.tokens, e.heads, e.hdim = self.m.tokens, self.m.heads, self.m.hdim
         e.div, e.add1, e.mul2 = kw.pop("div", 1.0), kw.pop("add1", 0.0), kw.pop("mul2", 1.0)

@@ -340,7 +340,10 @@ class QTensor:
         if isinstance(self._zero_point, K.ZpTerm) or self._bias is not None:
             raise ValueError("transpose of a q_matmul output is not on the QModel path")
         perm = list(range(self.dev.ndim))[::-1]
-        return self._moved(permute(self.dev, perm), perm, self._zero_point)
+        out = self._moved(permute(self.dev, perm), perm, self._zero_point)
+        # the transpose of a weight (a Gemm with transB) is still one for matmul's width rule
+        out._of_weight = getattr(self, "_is_weight", False) or getattr(self, "_of_weight", False)
+        return out
 
     def reshape(self, shape: ITensor):
         tgt = _reshape_target(self.dev.shape, shape.data)
@@ -401,7 +404,11 @@ class QTensor:
         return self._bt
 
     def matmul(self, other: "QTensor"):
-        assert self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
+        # a weight may be narrower than the activation it multiplies (QModel.weight_bit_width):
+        # q_matmul is the same integer product; two non-weight operands have one width
+        narrow_w = ((getattr(other, "_is_weight", False) or getattr(other, "_of_weight", False))
+                    and other.bit_width <= self.bit_width)
+        assert narrow_w or self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
         bt = col = None
         if other._bt is not None or getattr(other, "_is_weight", False):
             if other.dev.dtype == np.int8 and other.dev.ndim == 2:
