@@ -568,6 +568,22 @@ typedef struct nqk_attention {
 } nqk_attention;
 int nqk_attention_fused(const int8_t* q, const int8_t* k, const int8_t* v, int8_t* ctx, int64_t batch_heads,
                         const nqk_attention* params);
+/* The same attention for NQK_ATTN_LONG_MIN_T <= tokens <= NQK_ATTN_LONG_MAX_T (ViT/16 at 240, 384,
+ * 512 px: 226, 577, 1025 tokens), with the same parameters, layouts, q_rows meaning and bit
+ * identity to the three-launch chain: one workgroup per (image, head, 16 query rows) keeps the
+ * block's f32 score rows [16][TP + 4] and int8 probabilities [16][TP + 16] in LDS (TP = tokens
+ * rounded up to 64), and V^T [64][TP + 16] afterwards in the scores' place.
+ * NQK_ATTN_LONG_MAX_T is the largest token count whose workgroup fits the CU's 160 KiB of LDS:
+ * 80 TP + 10 880 bytes <= 163 840 gives TP <= 1912, so TP = 1856.
+ * Refused (an error, nothing launched): tokens outside the range (nqk_attention_fused takes the
+ * shorter ones), hdim != 64, null or misaligned pointers, scales or the divisor outside
+ * [2^-100, 2^100], |zq|,|zk| > 4096, |zp_p|,|zv| > 1024, and zero points whose int32 terms could
+ * overflow at this token count:
+ * tokens * (16384 + 128 (|zp_p| + |zv|) + |zp_p zv|) >= 2^31 (likewise over 64 for zq, zk). */
+#define NQK_ATTN_LONG_MIN_T 225
+#define NQK_ATTN_LONG_MAX_T 1856
+int nqk_attention_long(const int8_t* q, const int8_t* k, const int8_t* v, int8_t* ctx, int64_t batch_heads,
+                       const nqk_attention* params);
 
 /* Diagnostic: on the device, compares the fast-division variants of NumPy's exp and the
  * reference's erf (used by the fused kernels) with the IEEE-division ones on all 2^32

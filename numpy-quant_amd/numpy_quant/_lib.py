@@ -17,6 +17,7 @@ ZP_NONE, ZP_SCALAR, ZP_ROW, ZP_COL, ZP_KCONST, ZP_FULL = 0, 1, 2, 4, 8, 16
 ADD, SUB, MUL, DIV = 0, 1, 2, 3
 NEG, EXP, ERF, SQRT, RELU, SIGMOID, RECIP, TANH = range(8)
 IMG_NHWC, IMG_NCHW = 0, 1
+ATTN_LONG_MIN_T, ATTN_LONG_MAX_T = 225, 1856  # NQK_ATTN_LONG_MIN_T / _MAX_T: nqk_attention_long's token range
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -130,6 +131,7 @@ SIGNATURES = {
     "nqk_softmax_quant": [_p, _p, _p, _l, _l, _l, _f, _l, _i],
     "nqk_transpose_pad_i8": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_attention_fused": [_p, _p, _p, _p, _l, _p],
+    "nqk_attention_long": [_p, _p, _p, _p, _l, _p],
     "nqk_selftest_fastmath": [_p, _p],
     "nqk_selftest_gelu_filter": [_p],
     "nqk_sgemm_embed": [_p, _p, _p, _p, _p, _p, _l, _l, _l, _l],

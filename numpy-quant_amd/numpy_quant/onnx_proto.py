@@ -468,3 +468,67 @@ def redimension(m: ModelProto, width: int, heads: int, mlp: int, seed: int = 0,
             a.t.set_array(v)
             count += 1
     return count
+
+
+def retoken(m: ModelProto, tokens: int | None = None, base: int = 197, image: int | None = None, patch: int = 16,
+            seed: int = 0) -> int:
+    """Change the sequence length of a ViT graph exported at `base` tokens (the reference's graphs:
+    197 = (224 / 16)^2 patches + CLS).
+
+    Encoder-layer and self-attention graphs take `tokens`: the token entry of the int64 Reshape
+    shape constants [b, t, heads, head_dim] / [b, t, width] and of the input / output value infos
+    is rewritten.  The classifier graph takes `image`, the side of its square input in pixels (a
+    multiple of `patch`): tokens = (image / patch)^2 + 1, the input's H and W are rewritten, and
+    every initializer with a `base`-token axis [1, base, width] (the position embeddings) is
+    re-synthesized at the new length (`synthetic_array`, same name and seed), so like `redimension`
+    this is only for graphs whose weights are synthetic.  Returns the number of tensors rewritten
+    (shape constants, initializers, graph inputs / outputs); a graph with none raises ValueError."""
+    if image is not None:
+        if image <= 0 or image % patch:
+            raise ValueError(f"retoken: image side {image} is not a positive multiple of the patch size {patch}")
+        grid = image // patch
+        if tokens is not None and tokens != grid * grid + 1:
+            raise ValueError(f"retoken: {tokens} tokens do not match a {image} px image ({grid * grid + 1})")
+        tokens = grid * grid + 1
+    if tokens is None or tokens < 1:
+        raise ValueError("retoken: a positive token count (or image=) is required")
+    base_side = None
+    if image is not None:
+        g0 = int(round((base - 1) ** 0.5))
+        if g0 * g0 + 1 != base:
+            raise ValueError(f"retoken: base {base} is no square patch grid + CLS")
+        base_side = g0 * patch
+    count = 0
+    for node in m.graph.node:
+        if node.op_type != "Constant":
+            continue
+        for a in node.attribute:
+            if a.name != "value" or a.t is None:
+                continue
+            v = a.t.to_array()
+            if v.dtype == np.int64 and v.ndim == 1 and v.shape[0] in (3, 4) and v[1] == base:
+                v = v.copy()
+                v[1] = tokens
+                a.t.set_array(v)
+                count += 1
+    if image is not None:
+        for t in m.graph.initializer:
+            dims = [int(d) for d in t.dims]
+            if len(dims) == 3 and dims[1] == base:
+                dims[1] = tokens
+                t.set_array(synthetic_array(t.name, tuple(dims), seed))
+                count += 1
+    for vi in list(m.graph.input) + list(m.graph.output):
+        if len(vi.shape) == 3 and vi.shape[1] == base:
+            vi.shape[1] = tokens
+            count += 1
+        elif image is not None and len(vi.shape) == 4 and vi.shape[2] == base_side and vi.shape[3] == base_side:
+            vi.shape[2] = vi.shape[3] = image
+            count += 1
+    if count == 0:
+        raise ValueError(f"retoken: the graph has no {base}-token shape constant, initializer or input")
+    # the recorded shapes of intermediate values follow (they are documentation only)
+    for vi in m.graph.value_info:
+        if len(vi.shape) >= 3:
+            vi.shape = [tokens if d == base else d for d in vi.shape]
+    return count

@@ -38,6 +38,27 @@ LN_GATHER = True
 SPLIT_STREAMS = True
 
 
+def attn_long_enabled() -> bool:
+    """The long-sequence one-kernel attention (nqk_attention_long) for layers past
+    nqk_attention_fused's 224 tokens; NQK_ATTN_LONG=0 keeps the three launches (the A/B leg)."""
+    return os.environ.get("NQK_ATTN_LONG", "1") != "0"
+
+
+def attn_long_accepts(tokens, hdim, bit_width, zq, zk, zp, zv, scales) -> bool:
+    """nqk_attention_long's own host checks (nqk.h), so that a plan never relies on its error
+    return: the token range, head size 64, the fixed zero-point limits, the int32 bounds of the
+    zero-point algebra at this token count, and scales / the divisor (`scales`) in [2^-100, 2^100]."""
+    if hdim != 64 or not (_lib.ATTN_LONG_MIN_T <= tokens <= _lib.ATTN_LONG_MAX_T) or not (2 <= bit_width <= 8):
+        return False
+    if abs(zq) > 4096 or abs(zk) > 4096 or abs(zp) > 1024 or abs(zv) > 1024:
+        return False
+    bs = 64 * (16384 + 128 * (abs(zq) + abs(zk)) + abs(zq * zk))
+    bp = tokens * (16384 + 128 * (abs(zp) + abs(zv)) + abs(zp * zv))
+    if bs >= 2 ** 31 or bp >= 2 ** 31:
+        return False
+    return all(2.0 ** -100 <= abs(float(np.float32(s))) <= 2.0 ** 100 for s in scales)
+
+
 Epilogue = _lib.Epilogue
 
 
@@ -764,6 +785,15 @@ class FusedLayer:
         zs = [_zp(self.p_head["q"]), _zp(self.p_head["k"]), _zp(self.p_sm), _zp(self.p_head["v"])]
         self.attn_fused = (FUSED_ATTENTION and m.hdim == 64 and 1 <= m.tokens <= 224 and
                            abs(zs[0]) <= 4096 and abs(zs[1]) <= 4096 and abs(zs[2]) <= 1024 and abs(zs[3]) <= 1024)
+        # past 224 tokens the long-sequence kernel (nqk_attention_long: the score rows of 16 queries
+        # in LDS), called per part exactly like the one above: the layer keeps the two-stream parts,
+        # the CLS tail, and needs no score / probability workspace
+        ph = self.p_head
+        self.attn_long = (FUSED_ATTENTION and not self.attn_fused and attn_long_enabled() and attn_long_accepts(
+            m.tokens, m.hdim, self.bw, *zs,
+            scales=(np.float32(ph["q"].scale) * np.float32(ph["k"].scale), m.div, self.p_sm.scale,
+                    np.float32(self.p_sm.scale) * np.float32(ph["v"].scale), self.p_ctx.scale)))
+        self.attn_one = self.attn_fused or self.attn_long   # one kernel per part, either of the two
         # round 6: at width 192 (ViT-Ti) a residual GEMM tile holds whole rows, so the LayerNorm that
         # reads its output (LN2 after the out-projection; the NEXT layer's LN1 after FFN-down, linked
         # by the Plan) runs inside its epilogue (nqk_epilogue.ln_out): 24 LayerNorm launches and their
@@ -868,14 +898,14 @@ class FusedLayer:
             raise ValueError(f"layer input {x.dev.shape} does not match the graph ({m.tokens}, {self.D})")
         H, Dh, F = m.heads, m.hdim, self.F
         Tp = (T + 15) // 16 * 16
-        w = ws.get(B, T, Tp, H, Dh, D, F, unfused_attention=not self.attn_fused)
+        w = ws.get(B, T, Tp, H, Dh, D, F, unfused_attention=not self.attn_one)
         if self.cls_tail:
             self._run_cls(ws, w, x, B, streams)
             return
         # x1 is layer-private scratch shared by all layers (halves touch disjoint rows);
         # x2 is the layer's output value
         x2 = DeviceArray((B, T, D), np.float32)
-        if not self.attn_fused:
+        if not self.attn_one:
             streams.join()  # the three-launch attention runs whole-batch on stream 0
             streams = _ONE_STREAM
         streams.halves(B, lambda s_idx, i0, nb: self._run_part(w, x.dev, w["x1"], x2, i0, nb))
@@ -956,8 +986,9 @@ class FusedLayer:
                           out=[q.ptr, k.ptr, v.ptr], bias=self.bias_qkv.ptr)
             _gemm(EPI_QKV, lnq, self._b(e, "qkv", self.bt_qkv), 1, Mrows, 3 * D, D, D, D, None, 0, 0, e)
         pq, pk, pv_ = self.p_head["q"], self.p_head["k"], self.p_head["v"]
-        if self.attn_fused:
-            # 3-6) one kernel per (image, head): scores, softmax, P V, context quantize
+        if self.attn_one:
+            # 3-6) one kernel per (image, head), or per 16 query rows of one past 224 tokens: scores,
+            # softmax, P V, context quantize
             a = _lib.Attention()
             a.heads, a.tokens, a.hdim, a.ld_out, a.bit_width, a.q_rows = H, T, Dh, D, bw, q_rows
             a.zq, a.zk = _zp(pq), _zp(pk)
@@ -966,7 +997,8 @@ class FusedLayer:
             a.s_pv, a.zv = _f32(np.float32(self.p_sm.scale) * np.float32(pv_.scale)), _zp(pv_)
             a.s_ctx, a.zp_ctx = _f32(self.p_ctx.scale), _zp(self.p_ctx)
             t0 = KM.TIMER.begin() if KM.TIMER is not None else None
-            call("nqk_attention_fused", q.vp, k.vp, v.vp, ctx.vp, nb * H, ctypes.byref(a))
+            call("nqk_attention_long" if self.attn_long else "nqk_attention_fused", q.vp, k.vp, v.vp, ctx.vp, nb * H,
+                 ctypes.byref(a))
             if t0 is not None:
                 qr = q_rows or T  # the query rows computed: K and V are read whole
                 KM.TIMER.end("attention", t0, (2 * 2 * nb * H * qr * T * Dh, nb * H * Dh * (qr + 2 * T) + nb * qr * D))
@@ -1268,8 +1300,8 @@ class Plan:
         # LN1 (the same workspace rows its QKV GEMM reads: equal layer dimensions)
         for (k0, a), (k1, b) in zip(self.steps, self.steps[1:]):
             if (k0 == "layer" and k1 == "layer" and a.ln_fuse and b.ln_fuse and b.m.x_in is a.m.x_out and
-                    (a.D, a.F, a.m.heads, a.m.hdim, a.m.tokens, a.attn_fused) ==
-                    (b.D, b.F, b.m.heads, b.m.hdim, b.m.tokens, b.attn_fused)):
+                    (a.D, a.F, a.m.heads, a.m.hdim, a.m.tokens, a.attn_fused, a.attn_long) ==
+                    (b.D, b.F, b.m.heads, b.m.hdim, b.m.tokens, b.attn_fused, b.attn_long)):
                 a.next_ln, b.ln1_by_prev = b, True
         # a fused layer (one-kernel attention) whose output is read only by the LayerNorm of an
         # LnGather that gathers token 0, and is no graph output: after K and V, every operation of
@@ -1280,7 +1312,7 @@ class Plan:
             layers = {id(l.m.x_out): l for k, l in self.steps if k == "layer"}
             for k, lg in self.steps:
                 layer = layers.get(id(lg.ln.inputs[0])) if k == "ln_gather" else None
-                if (layer is not None and layer.attn_fused and len(layer.m.x_out.outputs) == 1 and
+                if (layer is not None and layer.attn_one and len(layer.m.x_out.outputs) == 1 and
                         not any(layer.m.x_out is o for o in qmodel.outputs) and lg.gathers_token0()):
                     layer.cls_tail, lg.cls_layer = True, layer
                     self.cls_tails += 1
