@@ -382,6 +382,16 @@ int nqk_minmax_f32(const float* x, int64_t n, float* out2, float* scratch, int64
 #define NQK_HIST_DIRECT_MAX 8192 /* measured: 5.0 us straight against 6.9 us through LDS at 8 Ki, 8.5 against 6.9 at 16 Ki */
 #define NQK_HIST_MAX_N ((int64_t)1 << 40)
 int nqk_hist_f32(const float* x, int64_t n, int64_t* state, int counts);
+/* Channel equalization (equalize.py; opt-in, not the reference's behaviour): the largest magnitude
+ * of every column (axis 0) or every row (axis 1) of x [rows][ld] (cols <= ld used), as bit patterns.
+ *   key(v) = bits(v) & 0x7FFFFFFF, every NaN -> 0x7FC00000 (uint32: monotone in |v|, NaN on top)
+ *   axis 0: state[c] = umax(state[c], key(x[r][c])) over all r, c < cols
+ *   axis 1: state[r] = umax(state[r], key(x[r][c])) over all c < cols, r < rows
+ * Read as float32 the state is np.abs(x).max(axis), NaN included, for every grid and every order of
+ * arrival.  A fresh state is all zero; every call accumulates.  rows == 0 or cols == 0: nothing to
+ * do.  x and state need 4-byte alignment only.  Fails before a launch on a NULL pointer, a negative
+ * size, cols > ld, cols > 2^31, rows > 2^40 or an axis other than 0 and 1. */
+int nqk_absmax_f32(const float* x, int64_t rows, int64_t cols, int64_t ld, int axis, uint32_t* state);
 /* Error statistics of a quantized model's value y against the float model's x (compare.py).
  * x is f32; y is f32 (scale, zp, has_zp ignored) or integer storage NQK_I8 .. NQK_I64 read as
  * f32(f64(q - zp) * f64(scale)), nqk_dequantize's expression with a scalar (has_zp) or no zero

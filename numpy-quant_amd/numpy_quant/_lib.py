@@ -114,6 +114,7 @@ SIGNATURES = {
     "nqk_normalize_axis": [_p, _p, _l, _l, _l, _f],
     "nqk_minmax_f32": [_p, _l, _p, _p, _l],
     "nqk_hist_f32": [_p, _l, _p, _i],
+    "nqk_absmax_f32": [_p, _l, _l, _l, _i, _p],
     "nqk_compare_stats": [_p, _p, _i, _f, _l, _i, _l, _p, _p, _l],
     "nqk_copy_strided": [_p, _p, _i, _i, _lp, _lp, _lp],
     "nqk_where_f32": [_p, _p, _p, _p, _i, _lp, _lp, _lp, _lp],

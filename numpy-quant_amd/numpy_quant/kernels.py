@@ -763,6 +763,42 @@ def histogram(x: DeviceArray, state: DeviceArray, counts: bool = True) -> None:
     _lib.call("nqk_hist_f32", x.vp, x.size, state.vp, 1 if counts else 0)
 
 
+ABSMAX_NAN_KEY = 0x7FC00000  # the key of every NaN in an nqk_absmax_f32 state
+
+
+def absmax(x: DeviceArray, state: DeviceArray, axis: int = 0, rows=None, cols=None, ld=None) -> None:
+    """Accumulate the largest magnitude of every column (axis 0) or row (axis 1) of float32 `x`,
+    read as [rows, ld] with `cols` columns used (default: a 2-D x as it lies), into `state`, uint32
+    [cols] or [rows] on the device (nqk_absmax_f32: the state viewed as float32 is
+    np.abs(x).max(axis)).  Asynchronous; everything is checked here, before the library is touched."""
+    if not isinstance(x, DeviceArray) or not isinstance(state, DeviceArray):
+        raise ValueError("absmax: x and state must be DeviceArrays")
+    if x.dtype != np.float32 or state.dtype != np.uint32:
+        raise ValueError(f"absmax: x must be float32 and state uint32 (got {x.dtype}, {state.dtype})")
+    if axis not in (0, 1):
+        raise ValueError(f"absmax: axis must be 0 or 1 (got {axis!r})")
+    if rows is None:
+        if x.ndim != 2:
+            raise ValueError("absmax: give rows, cols and ld for an array that is not 2-D")
+        rows, cols = x.shape
+    rows, cols = int(rows), int(cols)
+    ld = cols if ld is None else int(ld)
+    if rows < 0 or cols < 0 or cols > ld:
+        raise ValueError(f"absmax: bad sizes (rows {rows}, cols {cols}, ld {ld})")
+    if state.shape != ((cols,) if axis == 0 else (rows,)):
+        raise ValueError(f"absmax: state must be uint32 [{cols if axis == 0 else rows}] (got {state.shape})")
+    if rows and cols and (rows - 1) * ld + cols > x.size:
+        raise ValueError(f"absmax: [{rows}, {cols}] with ld {ld} reaches past the {x.size} elements of x")
+    if x.ptr % 4 or state.ptr % 4:
+        raise ValueError("absmax: x and state need 4-byte alignment")
+    for arr, what in ((x, "x"), (state, "state")):
+        if arr.ptr < arr.block.ptr or arr.ptr + arr.nbytes > arr.block.ptr + arr.block.size:
+            raise ValueError(f"absmax: {what} reaches outside its buffer")
+    if rows == 0 or cols == 0:
+        return
+    _lib.call("nqk_absmax_f32", x.vp, rows, cols, ld, axis, state.vp)
+
+
 CMP_STATE = 8            # NQK_CMP_STATE: words of a comparison state
 CMP_CHUNK = 4096         # NQK_CMP_CHUNK: elements per chunk partial
 CMP_MAX_N = 1 << 36      # NQK_CMP_MAX_N

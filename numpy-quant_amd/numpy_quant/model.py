@@ -293,6 +293,8 @@ class Model:
         # an images.ImagePreprocess: uint8 image batches are then accepted as inputs
         # (normalized and moved to NCHW on the device); None: uint8 is refused
         self.image_preprocess = None
+        # an equalize.Equalization on the result of Model.equalize (its sites and their vectors)
+        self.equalization = None
 
     def __repr__(self):
         return f"Model({len(self.nodes)} nodes, {len(self.values)} values, inputs={self.inputs}, outputs={self.outputs})"
@@ -418,6 +420,22 @@ class Model:
                 flat = d.reshape((d.shape[0], -1) if d.shape else (-1,))
                 vmin[val.name], vmax[val.name] = np.mean(flat.min()), np.mean(flat.max())
         return vmin, vmax
+
+    def equalize(self, batches, alpha=0.5, emax=8, pow2=True) -> "Model":
+        """Channel equalization (equalize.py; not the reference's behaviour): a new float Model over
+        the same graph in which every LayerNorm that feeds only MatMul weights has its gamma and beta
+        divided by a per-channel vector s[k] and row k of those weights multiplied by s[k], so that
+        the LN output the quantizer sees is flat.  s comes from the channel maxima of the LN outputs
+        over `batches` (an iterable of input lists, one float forward each, accumulated on the
+        device) and of the weights' rows: s[k] = 2^e[k], e[k] = clip(rint(r[k] - median(r)), -emax,
+        emax), r[k] = alpha log2 a[k] - (1 - alpha) log2 w[k]; `pow2=False` keeps the exponent
+        unrounded.  With pow2 the result computes the source's float outputs bit for bit.  `self` is
+        not changed and shares every other constant with the result, whose `equalization` lists
+        the sites and their vectors.  Quantize the result as any other Model."""
+        from .equalize import equalize
+        if isinstance(self, QModel):
+            raise ValueError("equalize: call it on the float Model, before it is quantized")
+        return equalize(self, batches, alpha, emax, pow2)
 
     def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
                  weight_bit_width=None):
