@@ -162,15 +162,15 @@ B_ATT, H_ATT = 2, 3
 SWITCH = -86.5  # the exponent-add exp variant's switch point (nqk_selftest_fastmath)
 
 
-@functools.lru_cache(maxsize=4)
-def attn_case(c):
+def _attn_operands(c, s_p=None):
     """q, k, v [6][T][64] with, per (batch, head): 0 random; 1 flat softmax rows (all keys equal);
     2 peaked rows (one key ahead by more than 104: every other exp is 0); 3 rows whose softmax
     arguments straddle -86.5; 4 all -128; 5 all 127.  s_qk is chosen so that the graded keys of
-    head 3 are 0.85 apart in score."""
+    head 3 are 0.85 apart in score.  With them the reference scores, P and its row sums, and the
+    measured row conditions."""
     T = c.T
     zq, zk, zp_p, zv = ZSETS[c.zset]
-    s_p, zp_sp = SP[c.sp]
+    s_p, zp_sp = (SP[c.sp][0] if s_p is None else s_p), SP[c.sp][1]   # (s_p given: attn_sum_case)
     zp_p = zp_sp if zp_p is None else zp_p
     rng = np.random.default_rng(zlib.crc32(repr(tuple(c)).encode()))
     lo, hi = (int(x) for x in O.qrange(c.bw))  # q, k, v hold bit_width-bit values (lo = -128, hi = 127 at 8)
@@ -186,8 +186,6 @@ def attn_case(c):
     q[4], k[4], v[4] = lo, lo, lo
     q[5], k[5], v[5] = hi, hi, hi
     s_qk = np.float32(0.85 * 8.0 / (DH * abs(cq - zq)))
-    s_v = np.float32(0.043)
-    s_pv = np.float32(np.float32(s_p) * s_v)
     div = 8.0
     stats = {}
     s = R.scores(q, k, zq, zk, s_qk, div)
@@ -202,6 +200,23 @@ def attn_case(c):
                              int(((arg[3] < SWITCH) & (arg[3] > SWITCH - 2)).sum()))
         if T >= 197:
             assert stats["straddle"][0] > 0 and stats["straddle"][1] > 0, stats
+    return dict(q=q, k=k, v=v, zq=zq, zk=zk, zp_p=zp_p, zv=zv, s_qk=s_qk, div=div, s_p=np.float32(s_p), scores=s, p=p,
+                psum=psum, stats=stats)
+
+
+@functools.lru_cache(maxsize=4)
+def attn_case(c):
+    """The operands of _attn_operands with a calibrated-looking context scale, and the reference of
+    every stage: scores, P and its row sums, V^T and its sums, the context."""
+    return _freeze(_attn_finish(c, _attn_operands(c)))
+
+
+def _attn_finish(c, d):
+    T = c.T
+    q, k, v, p, zq, zk, zp_p, zv, s_qk, div, s_p, stats = (d[x] for x in "q k v p zq zk zp_p zv s_qk div s_p stats".split())
+    lo, hi = (int(x) for x in O.qrange(c.bw))
+    s_v = np.float32(0.043)
+    s_pv = np.float32(s_p * s_v)
     # a calibrated-looking context scale: the dequantized P.V values fill the int8 range
     acc, z = R._full_acc(p[..., :T], v, zp_p, zv, T)
     dctx = O.dequantize(acc, s_pv, z)
@@ -211,8 +226,82 @@ def attn_case(c):
     stats["ctx_clipped"] = float(((ctx == lo) | (ctx == hi)).mean())
     assert np.array_equal(ctx, R.attention(q, k, v, H_ATT, zq, zk, s_qk, div, s_p, zp_p, s_pv, zv, s_ctx, zp_ctx, c.bw))
     vt, vsum = R.transpose_pad(v, (T + 15) // 16 * 16)
-    return _freeze(dict(q=q, k=k, v=v, zq=zq, zk=zk, zp_p=zp_p, zv=zv, s_qk=s_qk, div=div, s_p=np.float32(s_p), s_pv=s_pv,
-                        s_ctx=s_ctx, zp_ctx=zp_ctx, scores=s, p=p, psum=psum, vt=vt, vsum=vsum, ctx=ctx, stats=stats))
+    return dict(d, s_pv=s_pv, s_ctx=s_ctx, zp_ctx=zp_ctx, vt=vt, vsum=vsum, ctx=ctx)
+
+
+@functools.lru_cache(maxsize=2)
+def attn_sum_case(T, sign):
+    """AttnCase(T, "std", "unit") with s_p moved from 1 / 255 by a few thousand f32 steps, to where
+    the LAST BIT of the softmax denominator shows in the context.  (With s_p = 1 / 255 or 8e-5 it does
+    not: summing a row of exps in another pairwise order changes the denominator of 8 .. 26 % of the
+    rows by one ulp and not one P.)  The rows of head 3 are identical (one query value, graded keys in
+    a random order: a sum with roundoff).  s_p is the f32 value nearest 1 / 255 at which the row's
+    largest probability (of those the neighbour changes) quantizes differently for the denominator and for its neighbour one ulp
+    above (sign = +1) or below (-1); asserted on the reference: with that neighbour as the
+    denominator of head 3, P changes in every row and the context in at least T elements."""
+    c = AttnCase(T, "std", "unit")
+    s = _attn_operands(c)["scores"][3, 0]
+    ex = np.exp(s + (-s.max()))
+    den = ex.sum()
+    assert ex.dtype == np.float32 and den.dtype == np.float32
+    alt = np.nextafter(den, np.float32(np.inf * sign))
+    base = np.float32(1.0 / 255).view(np.int32)
+    cand = (base + np.arange(-200000, 200001, dtype=np.int32)).view(np.float32)
+    zp, s_p = np.int64(SP["unit"][1]), None
+    for j in np.argsort(-ex)[:8]:  # the largest probability that the neighbour changes at all
+        p_ref, p_alt = ex[j] / den, ex[j] / alt
+        hit = np.flatnonzero(O.quantize(p_ref / cand, 8, np.float32(1), zp) != O.quantize(p_alt / cand, 8, np.float32(1), zp))
+        if p_ref != p_alt and hit.size:
+            s_p = cand[hit[np.abs(hit - 200000).argmin()]]
+            break
+    assert s_p is not None, "no scale within 200 000 steps of 1 / 255 puts one of the 8 largest probabilities on a boundary"
+    d = _attn_finish(c, _attn_operands(c, s_p=s_p))
+    assert np.array_equal(d["p"][3, 0, :T], O.quantize(ex / den, 8, s_p, zp))  # the oracle's Softmax, restated
+    p2 = d["p"].copy()
+    p2[3, :, :T] = O.quantize(ex / alt, 8, s_p, zp)
+    ctx2 = R.pv(p2, d["v"], d["zp_p"], d["zv"], d["s_pv"], d["s_ctx"], d["zp_ctx"], 8, H_ATT, T)
+    d["stats"].update(s_p_steps=int(s_p.view(np.int32)) - int(base), p_changed=int((p2 != d["p"]).sum()),
+                      ctx_changed=int((ctx2 != d["ctx"]).sum()))
+    assert d["stats"]["p_changed"] >= T and d["stats"]["ctx_changed"] >= T, d["stats"]
+    return _freeze(d)
+
+
+EXACT_T = (577, 1618)  # 1618: the most tokens nqk_attention_long's int32 bound admits at |zp_p| = |zv| = 1024
+
+
+@functools.lru_cache(maxsize=2)
+def attn_exact_case(T, zset):
+    """The int32 zero-point algebra of the context at the zero-point limits (zset "lim+" / "lim-",
+    the operands of _attn_operands), resolved to one part in 2^(31 - e): with s_pv = 2^-13 and
+    s_ctx = 2^(e - 13) the context is zp_ctx + (acc - z) / 2^e exactly, one step per 2^e int32 units,
+    centred on the median of acc - z over the four heads with random V (zp_ctx).  e is the smallest
+    integer at which under 2 % of those heads' reference context is clipped; they must then hold
+    at least 64 distinct values.  (With |zp_p| = 1024 every P clamps to 127 or -128, so the context
+    of a head varies over its 64 dimensions only: 256 values at the most.)"""
+    assert zset in ("lim+", "lim-")
+    d = _attn_operands(AttnCase(T, zset, "unit"))
+    p, v, zp_p, zv = d["p"], d["v"], d["zp_p"], d["zv"]
+    s_pv = np.float32(2.0 ** -13)
+    acc, z = R._full_acc(p[..., :T], v, zp_p, zv, T)
+    w = acc - z
+    stats = dict(d["stats"], acc_absmax=int(np.abs(w).max()))
+    assert stats["acc_absmax"] < 1 << 31, stats
+    med = float(np.median(w[:4]))
+    for e in range(31):
+        s_ctx = np.float32(2.0 ** (e - 13))
+        zp_ctx = int(-np.rint(med / 2.0 ** e))
+        c4 = O.quantize(O.dequantize(acc[:4], s_pv, z[:4]), 8, s_ctx, np.int64(zp_ctx))
+        clip = float(((c4 == -128) | (c4 == 127)).mean())
+        if clip < 0.02:
+            break
+    stats.update(e=e, clip_share=clip, distinct=int(len(np.unique(c4))))
+    assert stats["clip_share"] < 0.02 and stats["distinct"] >= 64, stats
+    ctx = R.pv(p, v, zp_p, zv, s_pv, s_ctx, zp_ctx, 8, H_ATT, T)
+    q, k = d["q"], d["k"]
+    assert np.array_equal(ctx, R.attention(q, k, v, H_ATT, d["zq"], d["zk"], d["s_qk"], d["div"], d["s_p"], zp_p, s_pv, zv,
+                                           s_ctx, zp_ctx, 8))
+    return _freeze(dict(q=q, k=k, v=v, zq=d["zq"], zk=d["zk"], zp_p=zp_p, zv=zv, s_qk=d["s_qk"], div=d["div"], s_p=d["s_p"],
+                        s_pv=s_pv, s_ctx=s_ctx, zp_ctx=zp_ctx, ctx=ctx, stats=stats))
 
 
 @functools.lru_cache(maxsize=1)
@@ -314,3 +403,25 @@ ATTN_CASES = [A(T, "std", sp) for T in (1, 16, 17, 197, 224) for sp in ("unit", 
 ATTN_CASES += [A(T, z, "unit") for z in ("lim+", "lim-", "limqk") for T in (17, 197)]
 ATTN_CASES += [A(197, "fast", sp) for sp in ("unit", "cal")]
 ATTN_CASES += [A(17, "std", "unit", _bw) for _bw in (2, 3)]
+
+# nqk_attention_long (225 .. 1856 tokens), each T the smallest at an edge of k_attn_long or of NumPy's
+# pairwise sum: 225 the first it takes (TP = 256: one key in the last 16-key score tile, one row in
+# the last query block); 256 | 257, 512 | 513, 1025 the pairwise-sum depths (257: five 64-key chunks,
+# 1025: seventeen, an odd count in the two-accumulator P V loop); 640 | 641 the 64 KiB default of
+# dynamic LDS (80 TP + 10 880 = 62 080 | 67 200 bytes); 1856 the last it takes.  (577 with the
+# limit zero points of Q and K: the ViT/16 count at 384 px.)  attn_case keeps four cases: the list
+# ascends in T and the stage list below descends, so a test over the one followed by a test over the
+# other finds the costly references (1856 and 1025 tokens: 2.5 and 0.5 s) still cached; every
+# reference below 641 tokens builds in under 0.2 s.
+LONG_T = (225, 256, 257, 512, 513, 640, 641, 1025, 1856)
+LONG_ATTN_CASES = []
+for _T in LONG_T:
+    LONG_ATTN_CASES += [A(_T, "std", sp) for sp in ("unit", "cal")]
+    if _T == 257:
+        LONG_ATTN_CASES += [A(257, "limqk", "unit")] + [A(257, "std", "unit", _bw) for _bw in (2, 3, 4)]
+    if _T == 513:
+        LONG_ATTN_CASES += [A(577, "limqk", "unit")]
+# the softmax denominator's last bit (attn_sum_case), at every depth of the pairwise sum
+SUM_T = (225, 257, 513, 1025)   # one, two, three and four splits
+# the three-launch chain past 224 tokens, stage by stage
+LONG_STAGE_CASES = [A(_T, "std", "cal") for _T in (1856, 1025, 641, 257, 225)] + [A(577, "limqk", "unit")]

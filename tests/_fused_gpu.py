@@ -1,10 +1,14 @@
 """Device-side setup of one nqk_qgemm_fused projection call from host operands, shared by
 tests/test_gpu_pgemm.py, tests/test_gpu_glut.py and tests/test_gpu_fused_reference.py: uploads,
 the weight images (row-major, nqk_pack_b, nqk_pack_b4, nqk_pack_pg, nqk_pack_pg4), the epilogue
-struct, zero-filled outputs, the launch, and the kernel id it took."""
+struct, zero-filled outputs, the launch, and the kernel id it took.  And of the attention calls
+(tests/test_gpu_fused_reference.py below 225 tokens, tests/test_gpu_attention_long_reference.py
+from there on): the nqk_attention struct of a case, and the three-launch chain stage by stage."""
 import ctypes
 
 import numpy as np
+
+import _fused_cases as F
 
 SQRT2_F32 = float(np.float32(1.4142135381698608))
 
@@ -94,3 +98,80 @@ def fused_gemm(epi_name, a_h, bt_h, *, zpa, bias_h, s_acc, s_out=(1.0, 1.0, 1.0)
     outs = [b.to_host() for b in bufs]
     del keep
     return kernel, outs, e
+
+
+# ------------------------------------------------------------------------------- attention
+def attn_params(d, heads, T, bw):
+    """The nqk_attention struct of an attention case (tests/_fused_cases.py attn_case / attn_exact_case)."""
+    from numpy_quant import _lib
+    a = _lib.Attention()
+    a.heads, a.tokens, a.hdim, a.ld_out, a.bit_width = heads, T, F.DH, heads * F.DH, bw
+    a.zq, a.zk, a.s_qk, a.div = d["zq"], d["zk"], float(d["s_qk"]), d["div"]
+    a.s_p, a.zp_p, a.s_pv, a.zv = float(d["s_p"]), d["zp_p"], float(d["s_pv"]), d["zv"]
+    a.s_ctx, a.zp_ctx = float(d["s_ctx"]), d["zp_ctx"]
+    return a
+
+
+def head_mismatches(got, want, T):
+    """Mismatch counts of a context [B][T][H * Dh] per (image, head)."""
+    g, w = (x.reshape(F.B_ATT, T, F.H_ATT, F.DH) for x in (got, want))
+    return [int((g[b, :, h] != w[b, :, h]).sum()) for b in range(F.B_ATT) for h in range(F.H_ATT)]
+
+
+def pv_gemm(d, p_h, vt_h, T, Tp, bw):
+    """EPI_PV of the case's parameters on host P [BH][T][Tp] and V^T [BH][Dh][Tp]; the context on the host."""
+    from numpy_quant import _lib
+    from numpy_quant.device import DeviceArray
+    from numpy_quant.plan import EPI_PV, _gemm
+    BH, Dh, H = F.B_ATT * F.H_ATT, F.DH, F.H_ATT
+    p, vt = DeviceArray.from_host(np.ascontiguousarray(p_h)), DeviceArray.from_host(np.ascontiguousarray(vt_h))
+    ctx = DeviceArray((F.B_ATT, T, H * Dh), np.int8)
+    ctx.fill_zero()
+    e = _lib.Epilogue()
+    e.bit_width, e.tokens, e.heads, e.hdim, e.ld_out, e.group_cols = bw, T, H, Dh, H * Dh, 1 << 30
+    e.zp_flags = _lib.ZP_ROW | _lib.ZP_COL | _lib.ZP_KCONST
+    e.zpa, e.zpb, e.kdim = d["zp_p"], d["zv"], T
+    e.s_acc[0], e.s_out[0], e.zp_out[0], e.out[0] = float(d["s_pv"]), float(d["s_ctx"]), d["zp_ctx"], ctx.ptr
+    e.div, e.add1, e.mul2 = 1.0, 0.0, 1.0
+    _gemm(EPI_PV, p, vt, BH, T, Dh, Tp, Tp, Tp, None, T * Tp, Dh * Tp, e)
+    assert _lib.load().nqk_qgemm_last_kernel() == 0
+    return ctx.to_host()
+
+
+def check_three_launch_pieces(case):
+    """The SCORES and PV epilogues (k_qgemm_epi, batched, row / column / K-constant zero-point
+    terms), nqk_softmax_quant and nqk_transpose_pad_i8 with their int64 sums, each fed with the
+    reference's own input of that stage and compared with the reference's output of it."""
+    from numpy_quant import _lib
+    from numpy_quant.device import DeviceArray
+    from numpy_quant.plan import EPI_SCORES, _gemm
+    d = F.attn_case(case)
+    T, BH, Dh, H, bw = case.T, F.B_ATT * F.H_ATT, F.DH, F.H_ATT, case.bw
+    Tp = (T + 15) // 16 * 16
+    dq, dk, dv = (DeviceArray.from_host(d[x].reshape(BH * T, Dh)) for x in "qkv")
+    # transpose + pad of V, with the sums over T
+    vt, vsum = DeviceArray((BH, Dh, Tp), np.int8), DeviceArray((BH, Dh), np.int64)
+    _lib.call("nqk_transpose_pad_i8", dv.vp, vt.vp, vsum.vp, BH, T, Dh, Tp)
+    np.testing.assert_array_equal(vt.to_host(), d["vt"])
+    np.testing.assert_array_equal(vsum.to_host(), d["vsum"])
+    # scores
+    s = DeviceArray((BH, T, T), np.float32)
+    e = _lib.Epilogue()
+    e.bit_width, e.tokens, e.heads, e.hdim, e.group_cols = bw, T, H, Dh, 1 << 30
+    e.zp_flags = _lib.ZP_ROW | _lib.ZP_COL | _lib.ZP_KCONST
+    e.zpa, e.zpb, e.kdim = d["zq"], d["zk"], Dh
+    e.s_acc[0], e.out[0] = float(d["s_qk"]), s.ptr
+    e.div, e.add1, e.mul2 = d["div"], 0.0, 1.0
+    _gemm(EPI_SCORES, dq, dk, BH, T, T, Dh, Dh, Dh, None, T * Dh, T * Dh, e)
+    assert _lib.load().nqk_qgemm_last_kernel() == 0
+    np.testing.assert_array_equal(s.to_host().view(np.int32), d["scores"].view(np.int32))
+    # softmax + quantize of the reference's scores
+    sr = DeviceArray.from_host(np.ascontiguousarray(d["scores"]))
+    p, psum = DeviceArray((BH, T, Tp), np.int8), DeviceArray((BH, T), np.int64)
+    p.fill_zero()
+    _lib.call("nqk_softmax_quant", sr.vp, p.vp, psum.vp, BH * T, T, Tp, float(d["s_p"]), d["zp_p"], bw)
+    np.testing.assert_array_equal(p.to_host(), d["p"])
+    np.testing.assert_array_equal(psum.to_host(), d["psum"])
+    # P . V on the reference's P and V^T
+    ctx = pv_gemm(d, d["p"], d["vt"], T, Tp, bw)
+    np.testing.assert_array_equal(ctx, d["ctx"])

@@ -29,6 +29,23 @@ def layer():
     return graph, qp, qc, vals
 
 
+@pytest.fixture(scope="module")
+def layer226():
+    """The same graph re-dimensioned to ViT-Ti (192 wide, 3 heads) and re-tokened to 226 (240 px):
+    past nqk_attention_fused's 224 tokens, where tests/test_gpu_attention_long_reference.py rests
+    on this reference."""
+    from numpy_quant import onnx_proto
+    proto = onnx_proto.load(os.path.join(MODELS, "vit_image_classifier_encoder_layer_no_weights.onnx"), synthetic_weights=True)
+    assert onnx_proto.redimension(proto, 192, 3, 768) > 0
+    assert onnx_proto.retoken(proto, 226) == 6
+    x = np.random.default_rng(226).standard_normal((1, 226, 192)).astype(np.float32)
+    graph = O.Graph(proto)
+    with np.errstate(all="ignore"):
+        qp, qc = O.calibrate(graph, [x], 8)
+        vals = O.quantized_forward(graph, qp, qc, [x], 8)
+    return graph, qp, qc, vals
+
+
 def _q(layer, name):
     """The quantized operand the oracle's MatMul makes of float value `name` (int64), its scale
     and zero point."""
@@ -77,28 +94,40 @@ def _attention_operands(layer):
     return _i8(q[0]), _i8(kt[0].transpose(0, 2, 1)), _i8(v[0]), (s_q, int(zq)), (s_k, int(zk)), (s_v, int(zv))
 
 
-def test_scores_softmax_context_match_oracle(layer):
+def _check_scores_softmax_context(layer, T, heads):
     _, qp, _, vals = layer
+    Tp = (T + 15) // 16 * 16
     q, k, v, (s_q, zq), (s_k, zk), (s_v, zv) = _attention_operands(layer)
     div = vals[AT + "Constant_3_output_0"][1]
     assert div.shape == () and float(div) == 8.0
     s = R.scores(q, k, zq, zk, s_q * s_k, float(div))
     np.testing.assert_array_equal(s.view(np.int32), vals[AT + "Div_output_0"][1][0].view(np.int32))
     pq, s_p, zp_p = _q(layer, AT + "Softmax_output_0")
-    p, rows = R.softmax_quant(s, 208, s_p, int(zp_p), 8)
-    np.testing.assert_array_equal(p[..., :197].astype(np.int64), pq[0])
-    assert not p[..., 197:].any()
+    p, rows = R.softmax_quant(s, Tp, s_p, int(zp_p), 8)
+    np.testing.assert_array_equal(p[..., :T].astype(np.int64), pq[0])
+    assert not p[..., T:].any()
     np.testing.assert_array_equal(rows, pq[0].sum(axis=-1))
     cq, s_c, zc = _q(layer, AT + "Reshape_3_output_0")
-    ctx = R.pv(p, v, int(zp_p), zv, s_p * s_v, s_c, int(zc), 8, 12, 197)
+    ctx = R.pv(p, v, int(zp_p), zv, s_p * s_v, s_c, int(zc), 8, heads, T)
     np.testing.assert_array_equal(ctx.astype(np.int64), cq)
     # the composition, and the transpose helper on V
-    np.testing.assert_array_equal(R.attention(q, k, v, 12, zq, zk, s_q * s_k, float(div), s_p, int(zp_p), s_p * s_v, zv,
+    np.testing.assert_array_equal(R.attention(q, k, v, heads, zq, zk, s_q * s_k, float(div), s_p, int(zp_p), s_p * s_v, zv,
                                               s_c, int(zc), 8), ctx)
-    vt, vsum = R.transpose_pad(v, 208)
-    np.testing.assert_array_equal(vt[:, :, :197], v.transpose(0, 2, 1))
-    assert not vt[:, :, 197:].any()
+    vt, vsum = R.transpose_pad(v, Tp)
+    np.testing.assert_array_equal(vt[:, :, :T], v.transpose(0, 2, 1))
+    assert not vt[:, :, T:].any()
     np.testing.assert_array_equal(vsum, v.astype(np.int64).sum(axis=1))
+    return q.shape
+
+
+def test_scores_softmax_context_match_oracle(layer):
+    assert _check_scores_softmax_context(layer, 197, 12) == (12, 197, 64)
+
+
+def test_scores_softmax_context_match_oracle_at_226_tokens(layer226):
+    """Rows of 226 scores (Tp = 240): the reference of the long-sequence attention tests rests on
+    the oracle's node loop, not on itself."""
+    assert _check_scores_softmax_context(layer226, 226, 3) == (3, 226, 64)
 
 
 def test_residual_sums_match_oracle(layer):

@@ -10,7 +10,14 @@ the figures found.
   are unclipped exact ties, with even and odd floors;
 * fused LayerNorm: under 28 % of the outputs clipped at every bit width and zero point;
 * attention: flat rows (all arguments 0), peaked rows (the runner-up 216.75 behind), and at
-  T >= 197 rows with 2 x T arguments within 2 above and 3 x T within 2 below -86.5."""
+  T >= 197 rows with 2 x T arguments within 2 above and 3 x T within 2 below -86.5;
+* the int32 algebra of the long attention at the zero-point limits (attn_exact_case): one context
+  step is 2^15 int32 units at 577 tokens (0.4 % | 1.2 % of the random heads' context clipped, 145 | 143
+  distinct values for "lim+" | "lim-") and 2^16 at 1618 tokens (0.4 %, 126 | 130 distinct values),
+  with |acc - z| up to 595 721 919 and 1 670 499 246 < 2^31;
+* the softmax denominator's last bit (attn_sum_case): s_p 28 196 | 28 197 f32 steps below or 55 108
+  above 1 / 255; the denominator's neighbour changes one P in each row of head 3 and 4112 .. 12 300
+  context elements."""
 import pytest
 
 import _fused_cases as F
@@ -51,3 +58,22 @@ def test_softmax_rows_have_the_stated_kinds(case):
         assert st["peak_gap"] > 104
     if case.T >= 197:
         assert st["straddle"][0] > 0 and st["straddle"][1] > 0
+
+
+@pytest.mark.parametrize("zset", ["lim+", "lim-"])
+@pytest.mark.parametrize("T", F.EXACT_T)
+def test_exact_cases_resolve_the_int32_algebra(T, zset):
+    st = F.attn_exact_case(T, zset)["stats"]
+    print(T, zset, st)
+    assert st["clip_share"] < 0.02 and st["distinct"] >= 64
+    assert st["e"] == {577: 15, 1618: 16}[T]    # the smallest such step: one less clips 2 % or more
+    assert st["acc_absmax"] < 1 << 31
+    assert st["peak_gap"] > 104 and st["straddle"][0] > 0 and st["straddle"][1] > 0
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+@pytest.mark.parametrize("T", F.SUM_T)
+def test_sum_cases_show_the_denominators_last_bit(T, sign):
+    st = F.attn_sum_case(T, sign)["stats"]
+    print(T, sign, st)
+    assert st["p_changed"] >= T and st["ctx_changed"] >= T and abs(st["s_p_steps"]) <= 200000

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import _fused_cases as F
+from _fused_gpu import attn_params, check_three_launch_pieces, head_mismatches, pv_gemm
 
 pytestmark = pytest.mark.gpu
 
@@ -202,16 +203,6 @@ def test_embed_q_tile_order_for_any_xcd_count(mfma, xcds, monkeypatch):
 
 
 # ------------------------------------------------------------------------------- attention
-def _attn_params(d, heads, T, bw):
-    from numpy_quant import _lib
-    a = _lib.Attention()
-    a.heads, a.tokens, a.hdim, a.ld_out, a.bit_width = heads, T, F.DH, heads * F.DH, bw
-    a.zq, a.zk, a.s_qk, a.div = d["zq"], d["zk"], float(d["s_qk"]), d["div"]
-    a.s_p, a.zp_p, a.s_pv, a.zv = float(d["s_p"]), d["zp_p"], float(d["s_pv"]), d["zv"]
-    a.s_ctx, a.zp_ctx = float(d["s_ctx"]), d["zp_ctx"]
-    return a
-
-
 _KERNELS = {"k_attention": ("0", "4"), "k_attn16": ("1", "4"), "k_attn16_nw5": ("1", "5")}
 
 
@@ -245,12 +236,10 @@ def test_attention_fused_equals_the_reference(case, kern, monkeypatch):
     dq, dk, dv = (DeviceArray.from_host(d[x].reshape(BH * T, F.DH)) for x in "qkv")
     ctx = DeviceArray((F.B_ATT, T, F.H_ATT * F.DH), np.int8)
     ctx.fill_zero()
-    a = _attn_params(d, F.H_ATT, T, case.bw)
+    a = attn_params(d, F.H_ATT, T, case.bw)
     _lib.call("nqk_attention_fused", dq.vp, dk.vp, dv.vp, ctx.vp, BH, ctypes.byref(a))
     got = ctx.to_host()
-    assert int((got != d["ctx"]).sum()) == 0, [int((got.reshape(F.B_ATT, T, F.H_ATT, F.DH)[b, :, h] !=
-                                                   d["ctx"].reshape(F.B_ATT, T, F.H_ATT, F.DH)[b, :, h]).sum())
-                                              for b in range(F.B_ATT) for h in range(F.H_ATT)]
+    assert int((got != d["ctx"]).sum()) == 0, head_mismatches(got, d["ctx"], T)
 
 
 @pytest.mark.parametrize("case", F.ATTN_CASES, ids=lambda c: "-".join(map(str, c)))
@@ -258,64 +247,13 @@ def test_three_launch_pieces_equal_the_reference(case):
     """The SCORES and PV epilogues (k_qgemm_epi, batched, row / column / K-constant zero-point
     terms), nqk_softmax_quant and nqk_transpose_pad_i8 with their int64 sums, each fed with the
     reference's own input of that stage."""
-    from numpy_quant import _lib
-    from numpy_quant.device import DeviceArray
-    from numpy_quant.plan import EPI_PV, EPI_SCORES, _gemm
-    d = F.attn_case(case)
-    T, BH, Dh, H, bw = case.T, F.B_ATT * F.H_ATT, F.DH, F.H_ATT, case.bw
-    Tp = (T + 15) // 16 * 16
-    dq, dk, dv = (DeviceArray.from_host(d[x].reshape(BH * T, Dh)) for x in "qkv")
-    # transpose + pad of V, with the sums over T
-    vt, vsum = DeviceArray((BH, Dh, Tp), np.int8), DeviceArray((BH, Dh), np.int64)
-    _lib.call("nqk_transpose_pad_i8", dv.vp, vt.vp, vsum.vp, BH, T, Dh, Tp)
-    np.testing.assert_array_equal(vt.to_host(), d["vt"])
-    np.testing.assert_array_equal(vsum.to_host(), d["vsum"])
-    # scores
-    s = DeviceArray((BH, T, T), np.float32)
-    e = _lib.Epilogue()
-    e.bit_width, e.tokens, e.heads, e.hdim, e.group_cols = bw, T, H, Dh, 1 << 30
-    e.zp_flags = _lib.ZP_ROW | _lib.ZP_COL | _lib.ZP_KCONST
-    e.zpa, e.zpb, e.kdim = d["zq"], d["zk"], Dh
-    e.s_acc[0], e.out[0] = float(d["s_qk"]), s.ptr
-    e.div, e.add1, e.mul2 = d["div"], 0.0, 1.0
-    _gemm(EPI_SCORES, dq, dk, BH, T, T, Dh, Dh, Dh, None, T * Dh, T * Dh, e)
-    assert _lib.load().nqk_qgemm_last_kernel() == 0
-    np.testing.assert_array_equal(s.to_host().view(np.int32), d["scores"].view(np.int32))
-    # softmax + quantize of the reference's scores
-    sr = DeviceArray.from_host(np.ascontiguousarray(d["scores"]))
-    p, psum = DeviceArray((BH, T, Tp), np.int8), DeviceArray((BH, T), np.int64)
-    p.fill_zero()
-    _lib.call("nqk_softmax_quant", sr.vp, p.vp, psum.vp, BH * T, T, Tp, float(d["s_p"]), d["zp_p"], bw)
-    np.testing.assert_array_equal(p.to_host(), d["p"])
-    np.testing.assert_array_equal(psum.to_host(), d["psum"])
-    # P . V on the reference's P and V^T
-    ctx = _pv(d, d["p"], d["vt"], T, Tp, bw)
-    np.testing.assert_array_equal(ctx, d["ctx"])
-
-
-def _pv(d, p_h, vt_h, T, Tp, bw):
-    from numpy_quant import _lib
-    from numpy_quant.device import DeviceArray
-    from numpy_quant.plan import EPI_PV, _gemm
-    BH, Dh, H = F.B_ATT * F.H_ATT, F.DH, F.H_ATT
-    p, vt = DeviceArray.from_host(np.ascontiguousarray(p_h)), DeviceArray.from_host(np.ascontiguousarray(vt_h))
-    ctx = DeviceArray((F.B_ATT, T, H * Dh), np.int8)
-    ctx.fill_zero()
-    e = _lib.Epilogue()
-    e.bit_width, e.tokens, e.heads, e.hdim, e.ld_out, e.group_cols = bw, T, H, Dh, H * Dh, 1 << 30
-    e.zp_flags = _lib.ZP_ROW | _lib.ZP_COL | _lib.ZP_KCONST
-    e.zpa, e.zpb, e.kdim = d["zp_p"], d["zv"], T
-    e.s_acc[0], e.s_out[0], e.zp_out[0], e.out[0] = float(d["s_pv"]), float(d["s_ctx"]), d["zp_ctx"], ctx.ptr
-    e.div, e.add1, e.mul2 = 1.0, 0.0, 1.0
-    _gemm(EPI_PV, p, vt, BH, T, Dh, Tp, Tp, Tp, None, T * Tp, Dh * Tp, e)
-    assert _lib.load().nqk_qgemm_last_kernel() == 0
-    return ctx.to_host()
+    check_three_launch_pieces(case)
 
 
 def test_pv_exact_ties():
     """EPI_PV with power-of-two scales: 0.75 % of the elements are exact ties (even and odd floors)."""
     d = F.pv_ties_case()
-    np.testing.assert_array_equal(_pv(d, d["p"], d["vt"], F.T_TOK, 208, 8), d["ctx"])
+    np.testing.assert_array_equal(pv_gemm(d, d["p"], d["vt"], F.T_TOK, 208, 8), d["ctx"])
 
 
 @pytest.mark.parametrize("field,value", [("zq", 4097), ("zq", -4097), ("zk", 4097), ("zk", -4097), ("zp_p", 1025),
@@ -327,7 +265,7 @@ def test_attention_rejects_zero_points_beyond_the_limits(field, value):
     T, BH = 17, F.B_ATT * F.H_ATT
     dq, dk, dv = (DeviceArray.from_host(d[x].reshape(BH * T, F.DH)) for x in "qkv")
     ctx = DeviceArray((F.B_ATT, T, F.H_ATT * F.DH), np.int8)
-    a = _attn_params(d, F.H_ATT, T, 8)
+    a = attn_params(d, F.H_ATT, T, 8)
     setattr(a, field, value)
     with pytest.raises(_lib.NQKError):
         _lib.call("nqk_attention_fused", dq.vp, dk.vp, dv.vp, ctx.vp, BH, ctypes.byref(a))

@@ -1,7 +1,8 @@
 """The fused plan on graphs past 224 tokens (onnx_proto.retoken): the layer takes the long-sequence
 one-kernel attention (plan.FusedLayer.attn_long, nqk_attention_long), keeps the two-stream parts
 and the CLS tail, allocates no score / probability workspace, and computes the node loop's bits;
-NQK_ATTN_LONG=0 keeps the three launches with the same bits."""
+NQK_ATTN_LONG=0 keeps the three launches with the same bits.  At batch 1 the node loop and both
+plans are also compared with the oracle's quantized_forward."""
 import os
 
 import numpy as np
@@ -63,6 +64,41 @@ def test_encoder_layer_226_tokens(quant, monkeypatch):
     assert plan.fused == 1 and not layer.attn_long and not layer.attn_fused
     np.testing.assert_array_equal(qmodel([x])[0], eager)
     assert "s" in plan.ws.bufs and "p" in plan.ws.bufs
+
+
+def test_encoder_layer_226_tokens_matches_oracle(monkeypatch):
+    """The same graph at batch 1 against the oracle's quantized_forward (as
+    test_gpu_plan.test_plan_encoder_layer_graph_matches_oracle at 197 tokens): the node loop, the
+    plan with nqk_attention_long and the plan with the three launches all compute the oracle's bits."""
+    from numpy_quant import onnx_proto
+    from numpy_quant.model import Model, QuantizationParams
+    from oracle import nq_oracle as O
+
+    def proto():
+        p = onnx_proto.load(os.path.join(MODELS, "vit_image_classifier_encoder_layer_no_weights.onnx"), synthetic_weights=True)
+        assert onnx_proto.redimension(p, 192, 3, 768) > 0
+        assert onnx_proto.retoken(p, 226) == 6
+        return p
+
+    x = np.random.default_rng(226).standard_normal((1, 226, 192)).astype(np.float32)
+    graph = O.Graph(proto())
+    with np.errstate(all="ignore"):
+        qp, qc = O.calibrate(graph, [x], 8)
+        ref = O.outputs_of(graph, O.quantized_forward(graph, qp, qc, [x], 8))[0]
+    assert ref.shape == (1, 226, 192)
+    qmodel = Model.from_onnx(proto()).quantize_with({k: QuantizationParams(v.scale, v.zero_point) for k, v in qp.items()},
+                                                    bit_width=8)
+    qmodel.keep_values = True
+    np.testing.assert_array_equal(qmodel([x])[0], ref)
+    qmodel.keep_values = False
+    monkeypatch.delenv("NQK_ATTN_LONG", raising=False)
+    (layer,) = _layers(qmodel.compile())
+    assert layer.attn_long and not layer.attn_fused
+    np.testing.assert_array_equal(qmodel([x])[0], ref)
+    monkeypatch.setenv("NQK_ATTN_LONG", "0")
+    (layer,) = _layers(qmodel.compile())
+    assert not layer.attn_long and not layer.attn_fused
+    np.testing.assert_array_equal(qmodel([x])[0], ref)
 
 
 def test_fused_attention_switch_forces_three_launches(monkeypatch):
