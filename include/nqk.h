@@ -548,10 +548,25 @@ int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64_t batch, i
  * per CU, B shared by its two row halves), 6 / 7 the same two with the GELU table epilogue
  * (nqk_gelu_lut_build); -1 none yet. */
 int nqk_qgemm_last_kernel(void);
-/* LayerNormalization (model.py:134-152) fused with the consumer MatMul's quantize */
+/* LayerNormalization (model.py:134-152) fused with the consumer MatMul's quantize:
+ * out[r][c] = quantize(((x[r][c] - mean_r) * (1 / sqrt(var_r + eps))) * gamma[c] + beta[c]), every f32 step
+ * rounded as NumPy rounds it (pairwise sums, correctly rounded division and square root, no contraction).
+ *   x, out: [rows][cols] contiguous; gamma, beta: [cols]; none may be NULL.
+ *   rows <= 0: nothing to do, returns 0 whatever the other arguments.  1 <= cols <= 8192 (the pairwise
+ *   plan's 64 leaves of up to 128); 1 <= bit_width <= 8 (the output is int8); other values are refused.
+ *   Any cols, alignment, scale and zero point compute the same bytes.  What they buy is speed:
+ *   cols in {192, 384, 768} with x, gamma, beta 16-byte and out 4-byte aligned and 2^-100 <= |scale| <= 2^100
+ *   take the register-tree kernels (rows through LDS while rows * cols * 4 < 2^31 bytes), and there
+ *   |zp| <= 2^20 takes the magic-number quantize instead of the f64 chain (NQK_LN_F64Q=1 keeps the f64
+ *   chain, NQK_LN_REG=1 skips LDS).  Everything else runs the generic one-row-per-wave kernel.
+ *   Rows that hold an inf or a NaN get unspecified bytes (the reference turns NaN into INT64_MIN, which
+ *   int8 cannot hold); the other rows of the call are not affected and no error is reported. */
 int nqk_ln_quant(const float* x, const float* gamma, const float* beta, int8_t* out, int64_t rows, int64_t cols,
                  float eps, float scale, int64_t zp, int bit_width);
-/* Softmax (tensor.py:211-218) fused with quantize; out row stride ldo (zero pad), int64 row sums */
+/* Softmax (tensor.py:211-218) fused with quantize; out row stride ldo >= cols (zero pad), int64 row sums
+ * (rowsum may be NULL; x and out may not).  rows <= 0 returns 0; 1 <= cols <= 8192 and 1 <= bit_width <= 8
+ * (the output is int8), other values are refused.  No alignment is required.  Rows that hold a NaN, or
+ * +inf, get unspecified bytes. */
 int nqk_softmax_quant(const float* x, int8_t* out, int64_t* rowsum, int64_t rows, int64_t cols, int64_t ldo,
                       float scale, int64_t zp, int bit_width);
 /* int8 [nb][R][C] -> [nb][C][Rp] (zero padded) and rowsum[nb][C] = sum over R (may be NULL) */

@@ -2085,6 +2085,9 @@ extern "C" int nqk_qgemm_last_kernel(void) { return g_last_gemm; }
 extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* beta, int8_t* out, int64_t rows,
                             int64_t cols, float eps, float scale, int64_t zp, int bit_width) {
   if (rows <= 0) return 0;
+  if (!x || !gamma || !beta || !out) return fail("nqk_ln_quant: null x, gamma, beta or out");
+  if (cols <= 0) return fail("nqk_ln_quant: cols <= 0");
+  if (bit_width < 1 || bit_width > 8) return fail("nqk_ln_quant: bit_width outside 1..8 (the output is int8)");
   PwPlan p;
   if (row_plan(cols, p)) return -1;
   const double lo = -__builtin_ldexp(1.0, bit_width - 1), hi = __builtin_ldexp(1.0, bit_width - 1) - 1.0;
@@ -2138,6 +2141,13 @@ extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* bet
   }
   const int64_t slice = (int64_t)(row_smem(cols) / sizeof(float) + 3) / 4 * 4;
   const unsigned grid = (unsigned)(((rows + 3) / 4) < 65536 * 4 ? (rows + 3) / 4 : 65536 * 4);
+  static bool lds_attr = false;  // rows of more than 3516 columns ask for more than the 64 KiB default of dynamic LDS
+  if (!lds_attr && 4 * slice * sizeof(float) > 65536) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_ln_quant), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(4 * row_smem(8192))) != hipSuccess)
+      (void)hipGetLastError();
+    lds_attr = true;
+  }
   hipLaunchKernelGGL(k_ln_quant, dim3(grid), dim3(256), 4 * slice * sizeof(float), stream(), x, gamma, beta, out,
                      rows, cols, eps, p, scale, (double)zp, lo, hi, slice);
   return launch_status("nqk_ln_quant");
@@ -2146,6 +2156,9 @@ extern "C" int nqk_ln_quant(const float* x, const float* gamma, const float* bet
 extern "C" int nqk_softmax_quant(const float* x, int8_t* out, int64_t* rowsum, int64_t rows, int64_t cols,
                                  int64_t ldo, float scale, int64_t zp, int bit_width) {
   if (rows <= 0) return 0;
+  if (!x || !out) return fail("nqk_softmax_quant: null x or out");
+  if (cols <= 0) return fail("nqk_softmax_quant: cols <= 0");
+  if (bit_width < 1 || bit_width > 8) return fail("nqk_softmax_quant: bit_width outside 1..8 (the output is int8)");
   if (ldo < cols) return fail("nqk_softmax_quant: ldo < cols");
   PwPlan p;
   if (row_plan(cols, p)) return -1;

@@ -10,6 +10,7 @@ from collections import namedtuple
 import numpy as np
 
 import _fused_ref as R
+import _ln_cases
 from oracle import nq_oracle as O
 
 GemmCase = namedtuple("GemmCase", "epi M N K kind bw zpa zpo wbits l1", defaults=("rand", 8, -5, "std", 8, False))
@@ -63,8 +64,13 @@ def gemm_case(c):
     M, N, K = c.M, c.N, c.K
     ng = 3 if c.epi == "qkv" else 1
     stats, rows = {}, None
+    ln_rows = _ln_rows_case(c) if c.kind.startswith("rows_") else None
     if c.kind == "extreme":
         a, bt, rows = _extreme_operands(c, rng)
+    elif ln_rows is not None:  # a = 0, zpa = 0, no bias: the epilogue's f32 row is the residual row exactly
+        assert c.epi == "resid_ln" and c.zpa == 0 and c.bw == 8
+        a = np.zeros((M, K), np.int8)
+        bt = rng.integers(-24, 25, size=(N, K)).astype(np.int8)
     else:
         wl = 8 if (c.wbits == 4 or c.kind == "ties") else 24
         a = rng.integers(-128, 128, size=(M, K), dtype=np.int8)
@@ -98,6 +104,8 @@ def gemm_case(c):
         if abs(zp_out[g]) >= 1 << 20:
             bias[g * G:(g + 1) * G] += np.float32(-zp_out[g] * np.float64(s_out[g]))
     res = rng.standard_normal((M, N)).astype(np.float32) if c.epi in ("resid", "resid_ln") else None
+    if ln_rows is not None:
+        bias, res = np.zeros(N, np.float32), ln_rows["x"]
     d = dict(a=a, bt=bt, col=col, bias=bias, resid=res, s_acc=s_acc, s_out=s_out, zp_out=zp_out, col_absmax=cmax,
              col_l1max=l1 if c.l1 else 0, heads=G // DH if c.epi == "qkv" else 0)
     lo, hi = O.qrange(c.bw)
@@ -105,6 +113,12 @@ def gemm_case(c):
         d["ref"] = R.qkv(a, bt, bias, c.zpa, s_acc, s_out, zp_out, c.bw, T_TOK, d["heads"], DH)
     elif c.epi == "resid":
         d["ref"] = [R.resid(a, bt, bias, res, c.zpa, s_acc[0])]
+    elif ln_rows is not None:
+        d.update(gamma=ln_rows["gamma"], beta=ln_rows["beta"], ln_scale=ln_rows["scale"], ln_zp=ln_rows["zp"],
+                 ln_eps=ln_rows["eps"], ln_case=ln_rows)
+        y, q = R.resid_ln(a, bt, bias, res, c.zpa, s_acc[0], d["gamma"], d["beta"], d["ln_eps"], d["ln_scale"], d["ln_zp"], c.bw)
+        assert np.array_equal(y.view(np.int32), res.view(np.int32)) and np.array_equal(q, ln_rows["ref"])
+        d["ref"] = [y, q]
     elif c.epi == "resid_ln":
         d["gamma"] = (1 + 0.1 * rng.standard_normal(N)).astype(np.float32)
         d["beta"] = (0.1 * rng.standard_normal(N)).astype(np.float32)
@@ -151,6 +165,15 @@ def gemm_case(c):
         assert stats["tie_share"] >= 0.005 and even > 0 and odd > 0, stats
     d["stats"] = stats
     return _freeze(d)
+
+
+def _ln_rows_case(c):
+    """The LayerNorm case (tests/_ln_cases.py, 192 columns) whose rows are the residual of a
+    "rows_<kind>" case; a trailing 5 in the kind selects eps = 1e-5 instead of 1e-12."""
+    kind = c.kind[len("rows_"):]
+    eps = _ln_cases.EPS[1] if kind.endswith("5") else _ln_cases.EPS[0]
+    assert c.N == 192
+    return _ln_cases.ln_case(_ln_cases.LnCase(kind.rstrip("5"), c.N, c.M, eps))
 
 
 # ------------------------------------------------------------------------------- attention
@@ -392,6 +415,11 @@ TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "
 # the fused LayerNorm of k_qgemm_big at N = 192: bit widths, ln_zp at +-2^20 (magic-number quantize) and beyond (f64)
 LN_CASES = [(C("resid_ln", 197 * 3, 192, 192, bw=_bw), ["big", "big_pack"]) for _bw in (2, 3, 8)]
 LN_CASES += [(C("resid_ln", 131, 192, 768, zpo=_z), ["big", "big_pack"]) for _z in ("0", "p20", "m20", "p20+1", "m20-1")]
+
+# the same kernel on residual rows whose int8 bytes see the last bit of the mean, the variance, 1 / sqrt and the last
+# multiply-add (tests/_ln_cases.py kinds a, b, bm, c), with both epsilons
+LN_ROW_CASES = [(C("resid_ln", 131, 192, 192, "rows_" + _k, zpa=0), ["big", "big_pack"])
+                for _k in ("a", "a5", "b", "b5", "bm", "bm5", "c", "c5")]
 
 # persistent routes: some workgroup walks >= 3 tiles and the last row tile is ragged (see the test's docstring)
 PERSIST_CASES = [(C("gelu", 1024 * 128 + 77, 64, 192, "small"), ["pg"]),

@@ -9,6 +9,10 @@ the figures found.
 * exact ties: 0.78 % (K = 192) and 0.69 % (K = 768) of the QKV elements, 0.75 % of the PV elements
   are unclipped exact ties, with even and odd floors;
 * fused LayerNorm: under 28 % of the outputs clipped at every bit width and zero point;
+* fused LayerNorm on residual rows of tests/_ln_cases.py (131 x 192): the conditions of
+  tests/test_ln_cases_ref.py hold at this shape (kind a: the sequential mean changes at least 4 of
+  64 rows, nothing clipped; b, bm: half at -128, none at 127, every mistake changes at least 4 rows;
+  c: mean 0, ties with even and odd floors, both clip bounds reached by under 10 %);
 * attention: flat rows (all arguments 0), peaked rows (the runner-up 216.75 behind), and at
   T >= 197 rows with 2 x T arguments within 2 above and 3 x T within 2 below -86.5;
 * the int32 algebra of the long attention at the zero-point limits (attn_exact_case): one context
@@ -48,6 +52,33 @@ def test_layernorm_outputs_not_all_clipped(case):
     st = F.gemm_case(case)["stats"]
     print(case, st)
     assert st["clipped"] < 0.5
+
+
+@pytest.mark.parametrize("case", [c for c, _ in F.LN_ROW_CASES], ids=lambda c: "-".join(map(str, c)))
+def test_layernorm_row_cases_show_the_last_bits(case):
+    """The residual-row cases of the fused LayerNorm (131 rows of 192 columns, the mistakes of
+    _ln_cases.ln_restated counted over the first 64): the f32 row equals the residual row (asserted
+    by the builder) and the conditions of tests/test_ln_cases_ref.py hold at this shape too."""
+    import _ln_cases as L
+    d = F.gemm_case(case)["ln_case"]
+    st = L.stats(d)
+    kind = case.kind[len("rows_"):].rstrip("5")
+    if kind == "a":
+        n = L.rows_changed(d, "mean_seq")
+        print(case, st, n)
+        assert st["at_lo"] == 0 and st["at_hi"] == 0 and n >= 4
+    elif kind in ("b", "bm"):
+        n = {m: L.rows_changed(d, m) for m in L.MISTAKES}
+        print(case, st, n)
+        assert st["at_lo"] == 0.5 and st["at_hi"] == 0 and st["distinct"] >= 128 and min(n.values()) >= 4
+    else:
+        even, odd = L.tie_shares(d)
+        print(case, st, even, odd)
+        assert (d["x"].mean(axis=-1) == 0).all() and 0 < st["at_lo"] < 0.1 and 0 < st["at_hi"] < 0.1
+        if not case.kind.endswith("5"):
+            assert even >= 0.05 and odd >= 0.05
+        else:   # var + eps != var: few ties remain
+            assert even > 0 and odd > 0
 
 
 @pytest.mark.parametrize("case", F.ATTN_CASES, ids=lambda c: "-".join(map(str, c)))

@@ -132,6 +132,16 @@ def test_fused_layernorm_equals_the_reference(case, route, f64q, monkeypatch):
     _check_gemm(case, route, monkeypatch, {"NQK_LN_F64Q": "1"} if f64q else None)
 
 
+@pytest.mark.parametrize("case,route", _params(F.LN_ROW_CASES))
+@pytest.mark.parametrize("f64q", [False, True])
+def test_fused_layernorm_on_rows_that_show_its_last_bits(case, route, f64q, monkeypatch):
+    """The same kernel with a = 0, zpa = 0 and no bias, so that its f32 row IS the residual row:
+    the ill-conditioned, one-ulp-resolving and exact-tie rows of tests/_ln_cases.py at 192 columns
+    (random residual rows do not see the order of the epilogue's sums, its 1 / sqrt or a fused
+    last step: tests/test_ln_cases_ref.py)."""
+    _check_gemm(case, route, monkeypatch, {"NQK_LN_F64Q": "1"} if f64q else None)
+
+
 @pytest.mark.parametrize("case,route", _params(F.PERSIST_CASES))
 def test_persistent_routes_walk_three_tiles(case, route, monkeypatch):
     """Some workgroup walks at least three tiles and the last row tile is ragged, at the narrowest
