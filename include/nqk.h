@@ -392,6 +392,28 @@ int nqk_hist_f32(const float* x, int64_t n, int64_t* state, int counts);
  * do.  x and state need 4-byte alignment only.  Fails before a launch on a NULL pointer, a negative
  * size, cols > ld, cols > 2^31, rows > 2^40 or an axis other than 0 and 1. */
 int nqk_absmax_f32(const float* x, int64_t rows, int64_t cols, int64_t ld, int axis, uint32_t* state);
+/* Weight clipping search (opt-in: Model.quantize(weight_clip="mse"); not the reference's behaviour).
+ * For every column n of w [rows][ld] (cols <= ld used) and every candidate g < G, with the
+ * arithmetic of nqk_quantize_cols / nqk_dequantize_cols element by element:
+ *   s         = f32(s0[n] * ratio[g])                                 one f32 multiply
+ *   q         = rint(clip(f32(w[k][n] / s), f32(lo), f32(hi)))        lo = -2^(bw-1), hi = 2^(bw-1) - 1
+ *   dq        = f32(f64(q) * f64(s))
+ *   d         = f64(w[k][n]) - f64(dq)
+ *   err[g][n] = sum_k RN64(d * d)                                     f64, no fma
+ *   index[n]  = the first g with the smallest err[g][n] (best = err[0][n]; a later g replaces it
+ *               only when err[g][n] < best), scale[n] = f32(s0[n] * ratio[index[n]])
+ * The f64 sum of a column is taken in one order, whatever the shape: partial j (j = 0..63) adds the
+ * terms of rows j, j + 64, j + 128, .. in increasing order to +0.0; then p[j] = p[j] + p[j ^ m] for
+ * all j at once, m = 32, 16, 8, 4, 2, 1; the 64 equal entries are err[g][n].
+ * A column whose s0 is 0 or not finite is returned as it is: scale = s0, index = 0, err = +0.0.  A
+ * NaN weight makes every err of its column NaN and its index 0.  err may be NULL.
+ * Fails before a launch on rows or cols < 1, ld < cols, G outside 1..64, bit_width outside 1..8, a
+ * NULL w, s0, ratio, scale or index, a misaligned pointer (4 bytes; err 8), cols >= 2^31 or
+ * rows > 2^40.  One workgroup per column, no scratch, no atomics. */
+int nqk_clip_search_cols(const float* w, int64_t rows, int64_t cols, int64_t ld,
+                         const float* s0 /* [cols] */, const float* ratio /* [G] */, int G, int bit_width,
+                         float* scale /* [cols] out */, int32_t* index /* [cols] out */,
+                         double* err /* [G][cols] out, may be NULL */);
 /* Error statistics of a quantized model's value y against the float model's x (compare.py).
  * x is f32; y is f32 (scale, zp, has_zp ignored) or integer storage NQK_I8 .. NQK_I64 read as
  * f32(f64(q - zp) * f64(scale)), nqk_dequantize's expression with a scalar (has_zp) or no zero

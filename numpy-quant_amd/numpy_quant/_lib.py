@@ -115,6 +115,7 @@ SIGNATURES = {
     "nqk_minmax_f32": [_p, _l, _p, _p, _l],
     "nqk_hist_f32": [_p, _l, _p, _i],
     "nqk_absmax_f32": [_p, _l, _l, _l, _i, _p],
+    "nqk_clip_search_cols": [_p, _l, _l, _l, _p, _p, _i, _i, _p, _p, _p],
     "nqk_compare_stats": [_p, _p, _i, _f, _l, _i, _l, _p, _p, _l],
     "nqk_copy_strided": [_p, _p, _i, _i, _lp, _lp, _lp],
     "nqk_where_f32": [_p, _p, _p, _p, _i, _lp, _lp, _lp, _lp],

@@ -210,6 +210,63 @@ def requantize_cols(acc: DeviceArray, scale: DeviceArray, zp, bias: DeviceArray 
     return _narrow_if_fits(out, dt) if widen else out
 
 
+CLIP_MAX_G = 64  # candidates of one nqk_clip_search_cols call
+
+
+def clip_ratios(steps: int) -> np.ndarray:
+    """float32 [steps]: ratio[g] = f32(1 - 0.5 g / steps), the factor in float64; ratio[0] = 1."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= CLIP_MAX_G:
+        raise ValueError(f"clip_steps must be an integer in 1..{CLIP_MAX_G} (got {steps!r})")
+    return (1.0 - 0.5 * np.arange(int(steps), dtype=np.float64) / float(steps)).astype(np.float32)
+
+
+def clip_search_cols(x: DeviceArray, s0, ratios, bit_width: int, want_err: bool = False, rows=None, cols=None,
+                     ld=None):
+    """The clipping search of every column of float32 `x`, read as [rows, ld] with `cols` columns used
+    (default: a 2-D x as it lies): for column n and candidate g the float64 squared error of
+    quantize_cols / dequantize_cols at `bit_width` with the scale f32(s0[n] * ratios[g]), in the
+    fixed order include/nqk.h states (nqk_clip_search_cols).  `s0` float32 [cols] and `ratios`
+    float32 [G], 1 <= G <= 64, on the host or the device.  Returns (scale float32 [cols], index
+    int32 [cols]) on the device: the first candidate with the smallest error and its scale; with
+    `want_err` also err float64 [G, cols].  A column whose s0 is 0 or not finite comes back as it
+    is, with index 0.  Asynchronous; everything is checked here, before the library is touched."""
+    if not isinstance(x, DeviceArray) or x.dtype != np.float32:
+        raise ValueError("clip_search_cols: x must be a float32 DeviceArray")
+    if rows is None:
+        if x.ndim != 2:
+            raise ValueError("clip_search_cols: give rows, cols and ld for an array that is not 2-D")
+        rows, cols = x.shape
+    rows, cols = int(rows), int(cols)
+    ld = cols if ld is None else int(ld)
+    if rows < 1 or cols < 1 or cols > ld:
+        raise ValueError(f"clip_search_cols: bad sizes (rows {rows}, cols {cols}, ld {ld})")
+    if (rows - 1) * ld + cols > x.size:
+        raise ValueError(f"clip_search_cols: [{rows}, {cols}] with ld {ld} reaches past the {x.size} elements of x")
+    if x.ptr % 4 or x.ptr < x.block.ptr or x.ptr + x.nbytes > x.block.ptr + x.block.size:
+        raise ValueError("clip_search_cols: x is misaligned or reaches outside its buffer")
+    if isinstance(bit_width, bool) or not isinstance(bit_width, (int, np.integer)) or not 1 <= bit_width <= 8:
+        raise ValueError(f"clip_search_cols: bit_width must be an integer in 1..8 (got {bit_width!r})")
+    vecs = []
+    for v, what, n in ((s0, "s0", cols), (ratios, "ratios", None)):
+        if not isinstance(v, DeviceArray):
+            v = np.asarray(v)
+            if v.dtype != np.float32:
+                raise ValueError(f"clip_search_cols: {what} must be float32 (got {v.dtype})")
+            v = DeviceArray.from_host(v)
+        if v.dtype != np.float32 or v.ndim != 1 or (n is not None and v.shape != (n,)):
+            raise ValueError(f"clip_search_cols: {what} must be a float32 vector" + (f" [{n}]" if n else ""))
+        vecs.append(v)
+    s0, ratios = vecs
+    G = ratios.shape[0]
+    if not 1 <= G <= CLIP_MAX_G:
+        raise ValueError(f"clip_search_cols: 1..{CLIP_MAX_G} candidates (got {G})")
+    scale, index = DeviceArray((cols,), np.float32), DeviceArray((cols,), np.int32)
+    err = DeviceArray((G, cols), np.float64) if want_err else None
+    _lib.call("nqk_clip_search_cols", x.vp, rows, cols, ld, s0.vp, ratios.vp, G, int(bit_width), scale.vp, index.vp,
+              err.vp if want_err else None)
+    return (scale, index, err) if want_err else (scale, index)
+
+
 def rowsum(a: DeviceArray, batch: int, rows: int, k: int, ld: int, bstride: int) -> DeviceArray:
     out = DeviceArray((batch * rows,), np.int64)
     _lib.call("nqk_rowsum", a.vp, a.code, out.vp, batch, rows, k, ld, bstride)

@@ -283,6 +283,42 @@ def weight_width(bit_width, weight_bit_width) -> int:
     return int(weight_bit_width)
 
 
+def clip_candidates(weight_clip, clip_steps, weight_bits):
+    """The candidate ratios of a weight clipping search, float32 [clip_steps] (kernels.clip_ratios),
+    or None for `weight_clip=None`.  Anything but None and "mse", a `clip_steps` outside 1..64 and
+    weights wider than the search's 8 bits raise ValueError."""
+    if weight_clip is None:
+        return None
+    if weight_clip != "mse":
+        raise ValueError(f'weight_clip must be None or "mse" (got {weight_clip!r})')
+    ratios = K.clip_ratios(clip_steps)
+    if weight_bits > 8:
+        raise ValueError(f"weight_clip searches weights of at most 8 bits (got {weight_bits}: set weight_bit_width)")
+    return ratios
+
+
+def searched_scale(tensor: FTensor, axis: int, bit_width: int, s0, ratios: np.ndarray):
+    """The scale of an eligible weight after the clipping search (nqk_clip_search_cols): of the
+    candidates f32(s0 * ratios[g]) the first with the smallest squared quantization error at
+    `bit_width`.  `s0` a float32 vector [N] (column_scales): every output column searches its own
+    scale, and the result is the vector.  `s0` a scalar: one candidate index for the tensor, the first
+    minimum of the columns' errors summed on the host (err.sum(axis=1) of the float64 [G, N] the
+    kernel returns, the only download), and the result is the scalar f32(s0 * ratios[g]).  The
+    columns lie on `axis` of the 2-D `tensor`, permuted as column_scales permutes them."""
+    dev = tensor.dev if axis % 2 == 1 else permute(tensor.dev, [1, 0])
+    if K.is_cols(s0):
+        scale, _ = K.clip_search_cols(dev, np.asarray(s0, dtype=np.float32), ratios, bit_width)
+        return scale.to_host()
+    s0 = np.float32(s0)
+    _, _, err = K.clip_search_cols(dev, np.full(dev.shape[1], s0, dtype=np.float32), ratios, bit_width, want_err=True)
+    total = err.to_host().sum(axis=1)
+    best = 0
+    for g in range(1, total.shape[0]):
+        if total[g] < total[best]:
+            best = g
+    return s0 * ratios[best]
+
+
 # ----------------------------------------------------------------------------- models
 class Model:
     def __init__(self, nodes: list[Node], values: list[Value], inputs: List[Variable], outputs: List[Variable]):
@@ -438,14 +474,19 @@ class Model:
         return equalize(self, batches, alpha, emax, pow2)
 
     def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
-                 weight_bit_width=None):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
         (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
         MatMul / Gemm weight gets one scale per output column (QModel.per_channel).
         `weight_bit_width=w` (not the reference's behaviour either, 1 <= w <= bit_width): the same
-        weights are quantized at w bits, everything else at bit_width (QModel.weight_bit_width)."""
-        weight_width(bit_width, weight_bit_width)  # refused before the calibration forward
+        weights are quantized at w bits, everything else at bit_width (QModel.weight_bit_width).
+        `weight_clip="mse"` (not the reference's behaviour either): the scale of each of the same
+        weights, per tensor or per column, is shrunk by the ratio 1 - 0.5 g / clip_steps, g <
+        clip_steps <= 64, that quantizes the weight with the smallest squared error, searched on the
+        device (QModel.weight_clip); g = 0 is the scale without the search."""
+        # refused before the calibration forward
+        clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool, bw=bit_width):
@@ -453,7 +494,7 @@ class Model:
             return QuantizationParams(s, z)
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
-                             weight_bit_width=weight_bit_width)
+                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -475,11 +516,15 @@ class Model:
         return cal.ranges()
 
     def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
-                        per_channel=False, weight_bit_width=None):
+                        per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
         `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
-        and maxima of the constants."""
-        weight_width(bit_width, weight_bit_width)
+        and maxima of the constants.  So is `weight_clip` with `clip_weights`: two clippers of the
+        same constants."""
+        clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
+        if weight_clip is not None and clip_weights:
+            raise ValueError("quantize_stream: weight_clip searches the scales of the weights; clip_weights does "
+                             "not combine with it")
         if per_channel and clip_weights:
             raise ValueError("quantize_stream: per_channel takes the exact per-column ranges of the weights; "
                              "clip_weights does not combine with it")
@@ -490,7 +535,7 @@ class Model:
             return QuantizationParams(s, z)
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
-                             weight_bit_width=weight_bit_width)
+                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -566,7 +611,7 @@ class Model:
         return blob.load(self, path)
 
     def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False,
-                 weight_bit_width=None):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here.
         `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
@@ -574,8 +619,12 @@ class Model:
         `weight_bit_width`: the width of the same eligible weights (range, scale and integers, per
         tensor or per column); every other constant, every activation and every bias (4 * bit_width)
         keeps `bit_width`.  `params(value, asym, bw)` then gives an eligible weight's parameters at
-        that width."""
+        that width.
+        `weight_clip="mse"`: the scale of every eligible weight, computed here at its width, goes
+        through the clipping search (searched_scale) with `clip_steps` candidates; given scales are
+        taken as they are."""
         wbw = weight_width(bit_width, weight_bit_width)
+        ratios = clip_candidates(weight_clip, clip_steps, wbw)
         constants = constants or {}
         wanted = {}
         if constants:
@@ -618,6 +667,9 @@ class Model:
                 axis = per_channel_axis(value) if per_channel else None
                 if axis is not None and not given:
                     p = QuantizationParams(column_scales(value.data, axis, cbw), None)
+                waxis = per_channel_axis(value)
+                if ratios is not None and waxis is not None and not given and value.name not in constants:
+                    p = QuantizationParams(searched_scale(value.data, waxis, cbw, p.scale, ratios), None)
                 if K.is_cols(p.scale):
                     if not per_channel:
                         raise ValueError(f"{value.name}: a scale vector is given, but per_channel is not set")
@@ -693,6 +745,7 @@ class Model:
         qmodel.integer_conv = bool(integer_conv)
         qmodel.per_channel = bool(per_channel)
         qmodel.weight_bit_width = wbw
+        qmodel.weight_clip = weight_clip
         return qmodel
 
 
@@ -727,6 +780,10 @@ class QModel(Model):
         # weight_bit_width <= 4 the fused plan packs the weights as nibbles under activations of any
         # width up to 8 (nqk_epilogue.w_bits).
         self.weight_bit_width = bit_width
+        # opt-in, not the reference's behaviour: "mse" when the scales of the same weights came out
+        # of the clipping search of Model.quantize(weight_clip="mse"), else None.  A record only:
+        # quant_params holds the chosen scales, and nothing downstream reads this.
+        self.weight_clip = None
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "
