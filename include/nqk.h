@@ -468,8 +468,8 @@ typedef struct nqk_epilogue {
   const float* resid;                   /* residual [M][N] (EPI_RESID)                  */
   float div, add1, mul2;                /* Div constant (8 / sqrt 2), GELU +1 and *0.5  */
   int32_t b_packed;                     /* 1: bt is an nqk_pack_b image; 2: nqk_pack_b4  */
-  const int32_t* colterm;               /* optional: col[n] * zpa as int32 (the persistent */
-                                        /* projection GEMM needs it; NULL: not used)     */
+  const int32_t* colterm;               /* optional: col[n] * zpa as int32 (k_pg needs it; */
+                                        /* NULL: not used)                                */
   const int8_t* bt_pg;                  /* optional: the nqk_pack_pg image of the same Bt;  */
                                         /* when set, the 16x16x64 persistent GEMM (k_pg)  */
                                         /* runs the cases it takes (NULL: not used)       */
@@ -559,13 +559,16 @@ int nqk_gelu_lut_capacity(void);
  * exact chain (tests). */
 int nqk_gelu_lut_check(float s_out, int64_t zp_out, int32_t bit_width, float div, float add1, float mul2,
                        const void* lut, const float* k, int32_t n, uint64_t* mismatches);
+/* Kernel order: k_pg where bt_pg is given and it takes the case, else k_qgemm_big (batch 1, K % 192
+ * == 0, N % 4 == 0, COL zero-point term with column sums, aligned outputs, no s_col), else
+ * k_qgemm_epi.  All three compute the same bits. */
 int nqk_qgemm_fused(int epi, const int8_t* a, const int8_t* bt, int64_t batch, int64_t M, int64_t N, int64_t K,
                     int64_t lda, int64_t ldb, const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
                     const nqk_epilogue* params);
 /* Which kernel the last nqk_qgemm_fused call launched (tests / diagnostics): 0 small tiles
- * (k_qgemm_epi), 1 128x256 tiles (k_qgemm_big), 2 retired and not reused (it was a ping-pong
- * 256x256 kernel, measured no faster and removed), 3 the
- * persistent projection GEMM with the epilogue overlapped (k_proj), 4 the persistent 16x16x64
+ * (k_qgemm_epi), 1 128x256 tiles (k_qgemm_big), 2 and 3 retired and not reused (a ping-pong
+ * 256x256 kernel, measured no faster and removed; the round-2 persistent 256x256 kernel, which
+ * no plan launched since k_pg), 4 the persistent 16x16x64
  * GEMM with two workgroups per CU (k_pg), 5 k_pg on 256 x 256 tiles (one 512-thread workgroup
  * per CU, B shared by its two row halves), 6 / 7 the same two with the GELU table epilogue
  * (nqk_gelu_lut_build); -1 none yet. */

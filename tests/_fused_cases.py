@@ -350,27 +350,27 @@ def pv_ties_case():
 
 # ------------------------------------------------------------------------------- case lists
 C = GemmCase
-_FB = ["epi", "big", "pg_fb", "proj_fb"]   # *_fb: the persistent kernels are offered the case and must decline it
-_F32 = ["epi", "big", "pg", "proj"]
+_FB = ["epi", "big", "pg_fb"]   # pg_fb: k_pg is offered the case and must decline it
+_F32 = ["epi", "big", "pg"]
 
 # every route at the smallest shapes that reach it (input 4: random data, small output scales)
 ROUTE_CASES = [
     (C("qkv", 131, 192, 192, "small"), ["epi", "big", "big_pack", "pg"]),
     (C("qkv", 197 * 3, 576, 192, "small"), ["epi", "big", "big_pack", "pg"]),
-    # (k_proj takes whole images only, M % tokens == 0: it must decline the partial last image, proj_fb)
-    (C("qkv", 300, 768, 768, "small"), ["epi", "big", "big_pack", "proj_fb", "pg", "pg_wm2"]),
-    (C("qkv", 256 + 77, 2304, 768, "small"), ["big", "proj_fb", "pg", "pg_wm2"]),
-    (C("qkv", 197 * 2, 768, 768, "small"), ["big", "proj", "pg_wm2"]),
-    (C("qkv", 197 * 2, 2304, 768, "small"), ["proj", "pg"]),
+    # (a partial last image, M % tokens != 0, and two whole images)
+    (C("qkv", 300, 768, 768, "small"), ["epi", "big", "big_pack", "pg", "pg_wm2"]),
+    (C("qkv", 256 + 77, 2304, 768, "small"), ["big", "pg", "pg_wm2"]),
+    (C("qkv", 197 * 2, 768, 768, "small"), ["big", "pg_wm2"]),
+    (C("qkv", 197 * 2, 2304, 768, "small"), ["big", "pg"]),
     (C("qkv", 197 * 3, 576, 3072, "small"), ["epi", "big"]),
     (C("resid", 131, 768, 192), ["epi", "big", "big_pack", "pg"]),
     (C("resid", 300, 768, 768), ["epi", "big", "big_pack", "pg", "pg_wm2"]),
-    (C("resid", 512, 768, 768), ["proj", "pg_wm2"]),
+    (C("resid", 512, 768, 768), ["big", "pg_wm2"]),
     (C("resid", 256 + 77, 768, 3072, l1=True), ["big", "pg", "pg_wm2"]),
-    (C("resid", 256, 768, 3072, l1=True), ["proj", "pg"]),
+    (C("resid", 256, 768, 3072, l1=True), ["big", "pg"]),
     (C("resid", 131, 3072, 192), ["big", "pg"]),
     (C("gelu", 131, 768, 192), ["epi", "big", "big_pack", "pg", "glut"]),
-    (C("gelu", 300, 3072, 768, "small"), ["big", "big_pack", "proj", "pg", "pg_wm2", "glut", "glut_wm2"]),
+    (C("gelu", 300, 3072, 768, "small"), ["big", "big_pack", "pg", "pg_wm2", "glut", "glut_wm2"]),
     (C("gelu", 197 * 3, 768, 768, "small"), ["epi", "pg", "glut"]),
     # s_out = 0.0008: the increasing branch alone needs > 1024 buckets of 0.885 s, so nqk_gelu_lut_build
     # returns n = 0; zp_out = 100 keeps the negative half of the GELU outputs unclipped
@@ -379,21 +379,21 @@ ROUTE_CASES = [
 ]
 # input 3: bit widths, output zero points, zpa
 for _bw in (2, 3):
-    ROUTE_CASES += [(C("qkv", 197 * 2, 768, 768, bw=_bw), ["epi", "big", "pg", "proj"]),
+    ROUTE_CASES += [(C("qkv", 197 * 2, 768, 768, bw=_bw), ["epi", "big", "pg"]),
                     (C("gelu", 300, 768, 768, bw=_bw), ["epi", "big", "pg"])]
 for _bw in (2, 3, 4):
     ROUTE_CASES += [(C("qkv", 300, 768, 768, bw=_bw, wbits=4), ["big_pack4", "pg4"]),
                     (C("gelu", 300, 768, 768, bw=_bw, wbits=4), ["big_pack4", "pg4"])]
 ROUTE_CASES += [(C("resid", 300, 768, 768, bw=4, wbits=4), ["big_pack4", "pg4"]),
                 (C("resid", 300, 768, 3072, bw=4, wbits=4), ["big_pack4", "pg4"])]
-for _e, _m in (("qkv", 197 * 2), ("gelu", 300)):  # QKV: two whole images (k_proj), ragged against 128 and 256 rows
+for _e, _m in (("qkv", 197 * 2), ("gelu", 300)):  # QKV: two whole images, ragged against 128 and 256 rows
     for _z in ("0", "p20", "m20"):
         ROUTE_CASES.append((C(_e, _m, 768, 768, zpo=_z), _F32))
     for _z in ("p20+1", "m20-1"):
         ROUTE_CASES.append((C(_e, _m, 768, 768, zpo=_z), _FB))
 for _e, _m in (("qkv", 197 * 2), ("gelu", 300), ("resid", 300)):
     for _z in (0, -128, 127):
-        ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=_z), ["epi", "big", "pg"] + (["proj"] if _e != "resid" else [])))
+        ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=_z), ["epi", "big", "pg"]))
     ROUTE_CASES.append((C(_e, _m, 768, 768, zpa=1 << 20), ["epi", "big", "big_pack"]))
 
 # input 1: accumulators at the f32-exactness bound, just below 2^24 and just above
@@ -402,15 +402,15 @@ for _z in (40, 43, 140):  # K = 768 without col_l1max: 2^14 K + 128 K zpa = 16 5
     _lo = _z == 40
     EXTREME_CASES += [(C("qkv", 131, 576, 768, "extreme", zpa=_z), ["epi", "big", "pg" if _lo else "pg_fb"]),
                       (C("gelu", 131, 768, 768, "extreme", zpa=_z), ["epi", "big", "pg" if _lo else "pg_fb"]),
-                      (C("resid", 256, 768, 768, "extreme", zpa=_z), ["big", "pg", "pg_wm2", "proj"])]
+                      (C("resid", 256, 768, 768, "extreme", zpa=_z), ["big", "pg", "pg_wm2"])]
 for _z in (2, 3):  # K = 3072 with col_l1max = 42 K: 128 L + L zpa = 16 773 120 / 16 902 144
-    EXTREME_CASES += [(C("resid", 256, 768, 3072, "extreme", zpa=_z, l1=True), ["big", "pg", "pg_wm2", "proj"]),
+    EXTREME_CASES += [(C("resid", 256, 768, 3072, "extreme", zpa=_z, l1=True), ["big", "pg", "pg_wm2"]),
                       (C("qkv", 131, 576, 3072, "extreme", zpa=_z, l1=True), ["big"]),
                       (C("gelu", 131, 768, 3072, "extreme", zpa=_z, l1=True), ["big"])]
 
 # input 2: exact ties
 TIES_CASES = [(C("qkv", 197 * 3, 576, 192, "ties"), ["epi", "big", "big_pack", "pg"]),
-              (C("qkv", 197 * 2, 768, 768, "ties"), ["big", "pg", "pg_wm2", "proj"])]
+              (C("qkv", 197 * 2, 768, 768, "ties"), ["big", "pg", "pg_wm2"])]
 
 # the fused LayerNorm of k_qgemm_big at N = 192: bit widths, ln_zp at +-2^20 (magic-number quantize) and beyond (f64)
 LN_CASES = [(C("resid_ln", 197 * 3, 192, 192, bw=_bw), ["big", "big_pack"]) for _bw in (2, 3, 8)]
@@ -423,8 +423,7 @@ LN_ROW_CASES = [(C("resid_ln", 131, 192, 192, "rows_" + _k, zpa=0), ["big", "big
 
 # persistent routes: some workgroup walks >= 3 tiles and the last row tile is ragged (see the test's docstring)
 PERSIST_CASES = [(C("gelu", 1024 * 128 + 77, 64, 192, "small"), ["pg"]),
-                 (C("gelu", 512 * 256 + 77, 64, 768, "small"), ["pg_wm2"]),
-                 (C("gelu", 16 * 256 + 77, 256, 768, "small"), ["proj8"])]
+                 (C("gelu", 512 * 256 + 77, 64, 768, "small"), ["pg_wm2"])]
 
 A = AttnCase
 ATTN_CASES = [A(T, "std", sp) for T in (1, 16, 17, 197, 224) for sp in ("unit", "cal")]

@@ -23,27 +23,23 @@ from _fused_gpu import attn_params, check_three_launch_pieces, head_mismatches, 
 
 pytestmark = pytest.mark.gpu
 
-_SWITCHES = ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID", "NQK_PROJ_RESID", "NQK_PROJ_GELU", "NQK_PG_WM",
+_SWITCHES = ("NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID", "NQK_PG_WM",
              "NQK_NO_GELU_FILTER", "NQK_NO_GLUT", "NQK_GLUT_NO1", "NQK_GLUT_NOWIDE", "NQK_NO_L1",
-             "NQK_PROJ_CUS", "NQK_LN_F64Q", "NQK_NO_BPACK", "NQK_NO_B4", "NQK_XCDS",
+             "NQK_LN_F64Q", "NQK_NO_BPACK", "NQK_NO_B4", "NQK_XCDS",
              "NQK_PG_NOS8")
-_PG = {"NQK_NO_PROJ": "1", "NQK_PG_WM": "1"}
-_PROJ = {"NQK_PROJ_RESID": "1", "NQK_PROJ_GELU": "1"}
+_PG = {"NQK_PG_WM": "1"}
 # route: (nqk_qgemm_last_kernel id, environment, weight operand, k_pg image, GELU table)
 ROUTES = {
     "epi": (0, {}, "plain", None, False),                    # no precomputed column sums: k_qgemm_epi
-    "big": (1, {"NQK_NO_PROJ": "1"}, "plain", None, False),
-    "big_pack": (1, {"NQK_NO_PROJ": "1"}, "pack", None, False),
-    "big_pack4": (1, {"NQK_NO_PROJ": "1"}, "pack4", None, False),
-    "proj": (3, _PROJ, "pack", None, False),
-    "proj8": (3, dict(_PROJ, NQK_PROJ_CUS="8"), "pack", None, False),
-    "proj_fb": (1, _PROJ, "pack", None, False),              # offered to k_proj, which must decline
+    "big": (1, {}, "plain", None, False),
+    "big_pack": (1, {}, "pack", None, False),
+    "big_pack4": (1, {}, "pack4", None, False),
     "pg": (4, _PG, "pack", "pg", False),
     "pg_fb": (1, _PG, "pack", "pg", False),                  # offered to k_pg, which must decline
     "pg4": (4, _PG, "pack4", "pg4", False),
-    "pg_wm2": (5, {"NQK_NO_PROJ": "1", "NQK_PG_WM": "2"}, "pack", "pg", False),
+    "pg_wm2": (5, {"NQK_PG_WM": "2"}, "pack", "pg", False),
     "glut": (6, _PG, "pack", "pg", True),
-    "glut_wm2": (7, {"NQK_NO_PROJ": "1", "NQK_PG_WM": "2"}, "pack", "pg", True),
+    "glut_wm2": (7, {"NQK_PG_WM": "2"}, "pack", "pg", True),
     "nolut": (4, _PG, "pack", "pg", True),                   # nqk_gelu_lut_build returns n = 0: the filtered chain
 }
 
@@ -145,16 +141,11 @@ def test_fused_layernorm_on_rows_that_show_its_last_bits(case, route, f64q, monk
 @pytest.mark.parametrize("case,route", _params(F.PERSIST_CASES))
 def test_persistent_routes_walk_three_tiles(case, route, monkeypatch):
     """Some workgroup walks at least three tiles and the last row tile is ragged, at the narrowest
-    N each route takes (one column tile: N = 64 for k_pg's GELU, 256 for k_proj).  A grid of G
+    N each route takes (one column tile: N = 64 for k_pg's GELU).  A grid of G
     workgroups over nt tiles gives some workgroup three as soon as nt >= 2 G + 1:
     * k_pg, 128-row tiles: G = 2 workgroups per CU = 512 on the MI355X's 256 CUs (pg_launch:
       slots), so nt = 1025 row tiles: M = 1024 * 128 + 77;
-    * k_pg, 256-row tiles (NQK_PG_WM=2): G = 256, nt = 513: M = 512 * 256 + 77;
-    * k_proj: G = min(nt, CUs), or NQK_PROJ_CUS of them (launch_proj): with NQK_PROJ_CUS=8,
-      nt = 17: M = 16 * 256 + 77 (its residual form needs M % 256 == 0, so the GELU form).
-      The launcher reads the switch on every call, so earlier k_proj launches of the process do not
-      matter: 8 workgroups over 17 tiles in 8 bands, the last band's workgroup walks tiles 14, 15 and
-      the ragged 16.
+    * k_pg, 256-row tiles (NQK_PG_WM=2): G = 256, nt = 513: M = 512 * 256 + 77.
     On a device with fewer CUs the workgroups walk more tiles, never fewer."""
     _check_gemm(case, route, monkeypatch)
 

@@ -92,7 +92,7 @@ def _gelu_gemm(M, N, K, s_out, zp, seed, table, monkeypatch, wm=0, wbits=8):
     a_h = rng.integers(-128, 128, size=(M, K), dtype=np.int8)
     bt_h = rng.integers(-24, 25, size=(N, K), dtype=np.int8) if wbits == 8 else rng.integers(-8, 8, size=(N, K), dtype=np.int8)
     bias_h = (0.05 * rng.standard_normal(N)).astype(np.float32)
-    for v in ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_NO_GLUT", "NQK_PG_WM"):
+    for v in ("NQK_NO_F32X", "NQK_NO_PG", "NQK_NO_GLUT", "NQK_PG_WM"):
         monkeypatch.delenv(v, raising=False)
     if wm:
         monkeypatch.setenv("NQK_PG_WM", str(wm))

@@ -313,11 +313,11 @@ def test_fused_gemm_where_k_pg_declines(epi, N, variant, M, K, pc):
     assert _same(got, want)
 
 
-def test_fused_gemm_fallbacks_at_an_extreme_zero_point_and_on_k_proj(monkeypatch):
+def test_fused_gemm_fallbacks_at_an_extreme_zero_point_and_without_k_pg(monkeypatch):
     """An output zero point past 2^20 (k_pg's f32 rounding holds it no longer): k_pg declines and
     k_qgemm_big's f64 quantize takes the nibble image.  (An input zero point cannot make k_pg alone
     decline: nqk_qgemm_fused's own int32 condition, 2^14 K + 128 K |zpa| < 0.98 2^31, is the stricter
-    one and refuses a nibble image first.)  NQK_NO_PG=1 at M = 256: the QKV call runs on k_proj (3)."""
+    one and refuses a nibble image first.)  NQK_NO_PG=1 at M = 256: the QKV call runs on k_qgemm_big (1)."""
     from numpy_quant._lib import NQKError
     for epi, N in (("qkv", 192), ("gelu", 256)):
         a, bt, kw, _, _ = _case(epi, PG_BM, N, 768, 127, False)
@@ -341,7 +341,7 @@ def test_fused_gemm_fallbacks_at_an_extreme_zero_point_and_on_k_proj(monkeypatch
     assert kernel == 4 and _same(got, want)
     monkeypatch.setenv("NQK_NO_PG", "1")
     kernel, got = _fused("qkv", a, bt, **kw)
-    assert kernel == 3 and _same(got, want)
+    assert kernel == 1 and _same(got, want)
     monkeypatch.delenv("NQK_NO_PG")
     # a nibble image cannot hold weights said to be wider
     a, bt, kw, _, _ = _case("resid", PG_BM, 256, 768, 0, False)

@@ -17,7 +17,7 @@ def _last_kernel():
     return _lib.load().nqk_qgemm_last_kernel()
 
 
-def _run(epi_name, M, N, K, s_out_scale, use_pg, no_f32x, monkeypatch, seed, kernel=2, bw=8, l1=False, proj=False):
+def _run(epi_name, M, N, K, s_out_scale, use_pg, no_f32x, monkeypatch, seed, kernel=2, bw=8, l1=False):
     from _fused_gpu import fused_gemm
     rng = np.random.default_rng(seed)
     a_h = rng.integers(-128, 128, size=(M, K), dtype=np.int8)
@@ -27,13 +27,8 @@ def _run(epi_name, M, N, K, s_out_scale, use_pg, no_f32x, monkeypatch, seed, ker
     bias_h = (0.05 * rng.standard_normal(N)).astype(np.float32)
     resid_h = rng.standard_normal((M, N)).astype(np.float32)
     zpa = -5
-    for k in ("NQK_NO_PROJ", "NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID"):
+    for k in ("NQK_NO_F32X", "NQK_NO_PG", "NQK_PG_NORESID"):
         monkeypatch.delenv(k, raising=False)
-    monkeypatch.delenv("NQK_PROJ_RESID", raising=False)
-    if proj:  # the round-2 persistent 256 x 256 kernel (k_proj) for the residual epilogue
-        monkeypatch.setenv("NQK_PROJ_RESID", "1")
-    else:
-        monkeypatch.setenv("NQK_NO_PROJ", "1")
     monkeypatch.setenv("NQK_PG_WM", str(kernel))
     if no_f32x:
         monkeypatch.setenv("NQK_NO_F32X", "1")
@@ -178,16 +173,4 @@ def test_pg_gemm_bw6_equals_big_tile(epi_name, M, N, K, s_out_scale, monkeypatch
     k1, got, _ = _run(epi_name, M, N, K, s_out_scale, True, False, monkeypatch, seed, 1, bw=6)
     assert (k0, k1) == (1, 4), (k0, k1)
     for x, y in zip(ref, got):
-        np.testing.assert_array_equal(x, y)
-
-
-@pytest.mark.parametrize("M,seed", [(256 * 197, 21), (256 * 4, 22)])
-def test_proj_resid_k3072_f32_dequant_equals_f64(M, seed, monkeypatch):
-    """the round-2 persistent residual kernel (k_proj, NQK_PROJ_RESID=1) at K = 3072,
-    reachable in f32 through the column-L1 bound (col_l1max), equals its f64-dequantize run
-    (NQK_NO_F32X=1) bit for bit."""
-    k1, f32, _ = _run("resid", M, 768, 3072, 1.0, False, False, monkeypatch, seed, 1, l1=True, proj=True)
-    k2, f64, _ = _run("resid", M, 768, 3072, 1.0, False, True, monkeypatch, seed, 1, l1=True, proj=True)
-    assert (k1, k2) == (3, 3), (k1, k2)
-    for x, y in zip(f32, f64):
         np.testing.assert_array_equal(x, y)

@@ -81,18 +81,11 @@ for name, (N, K, epi) in shapes.items():
     def plain():
         _lib.call("nqk_qgemm_i8", a.vp, bt0.vp, c32.vp, 1, M, N, K, K, K, N, None, 0, 0, 0)
 
-    def oldk():
-        os.environ["NQK_NO_PROJ"] = "1"
-        try:
-            fused()
-        finally:
-            del os.environ["NQK_NO_PROJ"]
-
     def null():
         _lib.call("nqk_qgemm_fused", 5, a.vp, bt.vp, 1, M, N, K, K, K, None, 0, 0, ctypes.byref(e))
 
     only = os.environ.get("GM_ONLY")  # e.g. "down:null_epi" (profiling one variant)
-    for tag, fn in (("fused", fused), ("old_big", oldk), ("null_epi", null)):
+    for tag, fn in (("fused", fused), ("null_epi", null)):
         if only and only != f"{name}:{tag}":
             continue
         ms = timeit(fn)

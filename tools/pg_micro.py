@@ -2,7 +2,7 @@
 """Projection-GEMM timing at the ViT-Base B=256 shapes (round 3): the persistent 16x16x64
 kernel (k_pg) of several builds of libnqk.so side by side in ONE process (interleaved
 rounds; MI355X_MICROARCH.md: never rank builds timed in different processes), plus the
-round-2 kernels (k_proj / k_qgemm_big) of the main build.
+one-tile-per-workgroup kernel (k_qgemm_big) of the main build.
 
   PGM_LIBS=name=path,...   extra builds (tools/pg_diag.sh) loaded next to the main one
   PGM_SHAPES=qkv,out,up,down
@@ -143,7 +143,7 @@ for name in sel:
             variants.append(("glut" if lname == "main" else f"glut:{lname}", lib, {}, "glut"))
             for vname, env in envs.items():
                 variants.append((f"glut:{vname}" if lname == "main" else f"glut:{lname}:{vname}", lib, env, "glut"))
-    variants.append(("r02", main, {"NQK_PROJ_GELU": "1"} if epi == 4 else {}, False))
+    variants.append(("big", main, {}, False))
     res = {v[0]: [] for v in variants}
     for _ in range(ROUNDS):
         for vname, lib, env, use_pg in variants:

@@ -7,7 +7,7 @@ import sys
 from collections import defaultdict
 
 tag = sys.argv[1]
-pat = sys.argv[2] if len(sys.argv) > 2 else "k_proj"
+pat = sys.argv[2] if len(sys.argv) > 2 else "k_pg"
 vals = defaultdict(list)
 for d in sorted(glob.glob(f"gpurun_out/pmc_{tag}_[0-9]")):
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
