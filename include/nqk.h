@@ -215,6 +215,19 @@ int nqk_qgemm_generic(const void* a, int a_dtype, const void* b, int b_dtype, in
                       int64_t batch, int64_t M, int64_t N, int64_t K, int64_t a_sm, int64_t a_sk,
                       int64_t b_sk, int64_t b_sn, int64_t ldc, const int64_t* bmap,
                       int64_t a_mat_stride, int64_t b_mat_stride, int64_t c_mat_stride);
+/* The same product for 9..16-bit activations on the int8 MFMAs, exact, int64 out (what
+ * nqk_qgemm_generic writes): a is int16, bt [N][K] is NQK_I8 (the image nqk_qgemm_i8 takes) or
+ * NQK_I16.  Layouts, batch map and strides (in elements of each operand) as nqk_qgemm_i8; K, lda
+ * and ldb multiples of 16, K zero-padded by the caller.  An int16 x enters as two signed bytes,
+ * xh = x >> 8 and xl = (x & 255) - 128 (x = 256 xh + xl + 128); each pair of planes is one int8
+ * MFMA product in an int32 accumulator, the two cross planes of int16 x int16 in one, and the
+ * planes meet in int64 with the sums over k that the offset 128 asks for.  The shared accumulator
+ * holds up to 2^15 K: K >= 2^16 is an error, as are a bt_dtype other than the two, null or
+ * misaligned (16-byte; c 8-byte) pointers, batch > 65535 and more than 2^31 - 1 tiles. */
+int nqk_qgemm_i16(const int16_t* a, const void* bt, int bt_dtype, int64_t* c, int64_t batch,
+                  int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                  const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
+                  int64_t c_mat_stride);
 
 /* ------------------------------------------- float32 GEMM (BLAS-order exact) */
 /* C = A[M][K] . B[K][N] (element strides a_sm/a_sk, b_sk/b_sn).  Every output element is the

@@ -313,6 +313,14 @@ MFMA_MIN_WORK = 1 << 15
 # nqk_qgemm_i8 accumulates in int32: |a * b| <= 2^14, so K products stay below 2^31 only while
 # K < 2^17 (K = 131072 of -128 * -128 is exactly 2^31).  Longer K goes to the int64 kernel.
 I8_MAX_K = 1 << 17
+# nqk_qgemm_i16 (int16 activations as two byte planes on the int8 MFMAs): its shared cross-plane
+# accumulator holds up to 2^15 per product, so the padded K stays below 2^16.  NQK_GEMM16=0 keeps
+# such products on nqk_qgemm_generic (the A/B leg; read at every call).
+I16_MAX_K = 1 << 16
+
+
+def _gemm16_enabled() -> bool:
+    return os.environ.get("NQK_GEMM16", "1") != "0"
 
 
 class KernelTimer:
@@ -389,13 +397,16 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
         _, bmap = batch_map(a_batch, b_batch)
     nb = int(math.prod(out_batch))
     na, nbb = int(math.prod(a_batch)), int(math.prod(b_batch))
-    use_mfma = (a.dtype == np.int8 and b.dtype == np.int8 and M * N * K >= MFMA_MIN_WORK and nb <= 65535
-                and K < I8_MAX_K)
+    kp = (K + 15) // 16 * 16
+    use_i8 = (a.dtype == np.int8 and b.dtype == np.int8 and M * N * K >= MFMA_MIN_WORK and nb <= 65535
+              and K < I8_MAX_K)
+    use_i16 = (a.dtype == np.int16 and b.dtype in (np.int8, np.int16) and M * N * K >= MFMA_MIN_WORK
+               and nb <= 65535 and kp < I16_MAX_K and _gemm16_enabled())
+    use_mfma = use_i8 or use_i16
     if use_mfma:
-        kp = (K + 15) // 16 * 16
         ap = a if K == kp else _pad_k(a, a.shape[:-1], K, kp)
         if b_transposed is None:
-            bt = DeviceArray(b_batch + (N, kp), np.int8)
+            bt = DeviceArray(b_batch + (N, kp), b.dtype)
             if K != kp:
                 bt.fill_zero()
             shape = b_batch + (N, K)
@@ -404,12 +415,20 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
             copy_strided(b, bt, shape, src_st, contiguous_strides(b_batch + (N, kp)))
         else:
             bt = b_transposed
-        acc = DeviceArray(out_batch + (M, N), np.int32)
         t0 = TIMER.begin() if TIMER is not None else None
-        _lib.call("nqk_qgemm_i8", ap.vp, bt.vp, acc.vp, nb, M, N, kp, kp, kp, N, _lib.i64arr(bmap),
-                  M * kp, N * kp, M * N)
-        if t0 is not None:
-            TIMER.end("qgemm_i8", t0, (2 * nb * M * N * K, nb * (M * K + N * K + 4 * M * N)))
+        if use_i8:
+            acc = DeviceArray(out_batch + (M, N), np.int32)
+            _lib.call("nqk_qgemm_i8", ap.vp, bt.vp, acc.vp, nb, M, N, kp, kp, kp, N, _lib.i64arr(bmap),
+                      M * kp, N * kp, M * N)
+            if t0 is not None:
+                TIMER.end("qgemm_i8", t0, (2 * nb * M * N * K, nb * (M * K + N * K + 4 * M * N)))
+        else:
+            acc = DeviceArray(out_batch + (M, N), np.int64)
+            _lib.call("nqk_qgemm_i16", ap.vp, bt.vp, bt.code, acc.vp, nb, M, N, kp, kp, kp, N, _lib.i64arr(bmap),
+                      M * kp, N * kp, M * N)
+            if t0 is not None:  # one int8 MFMA product per pair of byte planes: 2 (int8 B) or 4
+                wb = bt.dtype.itemsize
+                TIMER.end("qgemm_i16", t0, (2 * nb * M * N * K * 2 * wb, nb * (2 * M * K + wb * N * K + 8 * M * N)))
     else:
         acc = DeviceArray(out_batch + (M, N), np.int64)
         _lib.call("nqk_qgemm_generic", a.vp, a.code, b.vp, b.code, acc.vp, nb, M, N, K, K, 1, N, 1, N,
@@ -443,7 +462,7 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
 
 
 def weight_bt(b: DeviceArray):
-    """Pre-transposed, K-padded int8 copy of a constant [K, N] weight and its
+    """Pre-transposed, K-padded copy of a constant int8 or int16 [K, N] weight and its
     column sums (used for every call instead of per-call transposes)."""
     K, N = b.shape[-2:]
     kp = (K + 15) // 16 * 16

@@ -275,7 +275,8 @@ class QTensor:
         self.scale = scale
         self._zero_point = zero_point
         self._bias = bias
-        self._bt = None  # cached (Bt, colsum) when this is a constant weight
+        self._bt = None  # cached (Bt, colsum) when this is a constant int8 weight
+        self._bt16 = None  # the same of a constant int16 weight (nqk_qgemm_i16's operand)
 
     @property
     def shape(self):
@@ -398,7 +399,11 @@ class QTensor:
         return QTensor(q, bit_width, scale, zero_point)
 
     def weight_operand(self):
-        """(Bt, colsum) of a constant int8 weight, computed once."""
+        """(Bt, colsum) of a constant int8 or int16 weight, computed once."""
+        if self.dev.dtype == np.int16:
+            if self._bt16 is None:
+                self._bt16 = K.weight_bt(self.dev)
+            return self._bt16
         if self._bt is None:
             self._bt = K.weight_bt(self.dev)
         return self._bt
@@ -410,8 +415,10 @@ class QTensor:
                     and other.bit_width <= self.bit_width)
         assert narrow_w or self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
         bt = col = None
-        if other._bt is not None or getattr(other, "_is_weight", False):
-            if other.dev.dtype == np.int8 and other.dev.ndim == 2:
+        if other._bt is not None or other._bt16 is not None or getattr(other, "_is_weight", False):
+            # an int16 weight only beside an int16 activation (nqk_qgemm_i16); a wider one never
+            if other.dev.ndim == 2 and (other.dev.dtype == np.int8 or
+                                        (other.dev.dtype == np.int16 and self.dev.dtype == np.int16)):
                 bt, col = other.weight_operand()
         if self._pc is not None:
             raise ValueError("matmul: a per-column scale belongs to the right operand (the weight) only")
