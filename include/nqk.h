@@ -228,6 +228,35 @@ int nqk_qgemm_i16(const int16_t* a, const void* bt, int bt_dtype, int64_t* c, in
                   int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                   const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
                   int64_t c_mat_stride);
+/* nqk_qgemm_i16 with the product's one consumer in its epilogue: the int64 product is never
+ * written.  Per output, exactly what nqk_dequantize(_cols) / nqk_requantize(_cols) compute from it:
+ *   v = acc + bias[n] - zpt[b][m][n]                 (int64; zpt from ROW | COL | KCONST, above)
+ *   d = f32( f64(v) * f64(s) )                       s = scale, or s_col[n]
+ *   out_dtype NQK_F32:  out = d                      (dequantize; no bias)
+ *   out_dtype NQK_I16:  out = nqk_requantize's tail of d with res_scale, res_zp, bit_width 9..16
+ * out [batch][M][ldo] of out_dtype, out_mat_stride in its elements; row / col are indexed through
+ * bmap as nqk_dequantize indexes them, zp_K is the unpadded K of the KCONST term.  Refused before
+ * any launch: what nqk_qgemm_i16 refuses (out aligned to its element), another out_dtype,
+ * bit_width outside 9..16 or a bias_dtype that is no integer code on the NQK_I16 form, a bias on the
+ * NQK_F32 form, NQK_ZP_SCALAR or NQK_ZP_FULL, a flag whose vector is NULL, ldo < N. */
+typedef struct nqk_gemm16_epilogue {
+  int32_t zp_flags;        /* NQK_ZP_NONE or ROW | COL | KCONST                     */
+  int32_t bias_dtype;      /* NQK_I8 .. NQK_I64 (read when bias is not NULL)         */
+  int32_t has_res_zp;
+  int32_t bit_width;       /* of the NQK_I16 result                                  */
+  float scale;             /* the product's scale (when s_col is NULL)               */
+  float res_scale;
+  int64_t zpa, zpb, zp_K;
+  int64_t res_zp;
+  const float* s_col;      /* [N] per-column scales, or NULL                         */
+  const int64_t* row;      /* rowsum(A) [a batch][M]                                 */
+  const int64_t* col;      /* colsum(B) [b batch][N]                                 */
+  const void* bias;        /* [N] of bias_dtype, or NULL                             */
+} nqk_gemm16_epilogue;
+int nqk_qgemm_i16_epi(const int16_t* a, const void* bt, int bt_dtype, void* out, int out_dtype,
+                      int64_t batch, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                      int64_t ldo, const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
+                      int64_t out_mat_stride, const nqk_gemm16_epilogue* params);
 
 /* ------------------------------------------- float32 GEMM (BLAS-order exact) */
 /* C = A[M][K] . B[K][N] (element strides a_sm/a_sk, b_sk/b_sn).  Every output element is the

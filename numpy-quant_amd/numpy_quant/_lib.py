@@ -53,6 +53,15 @@ class Attention(ctypes.Structure):
                 ("s_ctx", ctypes.c_float), ("pad1", ctypes.c_float), ("zp_ctx", ctypes.c_int64)]
 
 
+class Gemm16Epilogue(ctypes.Structure):
+    """Mirror of `nqk_gemm16_epilogue` (include/nqk.h)."""
+    _fields_ = [("zp_flags", ctypes.c_int32), ("bias_dtype", ctypes.c_int32), ("has_res_zp", ctypes.c_int32),
+                ("bit_width", ctypes.c_int32), ("scale", ctypes.c_float), ("res_scale", ctypes.c_float),
+                ("zpa", ctypes.c_int64), ("zpb", ctypes.c_int64), ("zp_K", ctypes.c_int64), ("res_zp", ctypes.c_int64),
+                ("s_col", ctypes.c_void_p), ("row", ctypes.c_void_p), ("col", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p)]
+
+
 SIGNATURES = {
     "nqk_init": [_i],
     "nqk_device_count": [ctypes.POINTER(_i)],
@@ -98,6 +107,8 @@ SIGNATURES = {
     "nqk_qgemm_i8": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
     "nqk_qgemm_generic": [_p, _i, _p, _i, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
     "nqk_qgemm_i16": [_p, _p, _i, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
+    "nqk_qgemm_i16_epi": [_p, _p, _i, _p, _i, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l,
+                          ctypes.POINTER(Gemm16Epilogue)],
     "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l, _l, _l],
     "nqk_sgemv_t": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_sgemv_small": [_p, _p, _p, _l, _l, _l],

@@ -323,6 +323,13 @@ def _gemm16_enabled() -> bool:
     return os.environ.get("NQK_GEMM16", "1") != "0"
 
 
+def _gemm16_epi_enabled() -> bool:
+    """NQK_GEMM16_EPI=1 opts in to nqk_qgemm_i16_epi; unset or 0 keeps nqk_qgemm_i16 and a separate
+    dequantize / requantize launch (the A/B leg; read at every call).  Opt-in because one of the four
+    model-level ranges of profiles/gemm16_epi.json overlaps."""
+    return os.environ.get("NQK_GEMM16_EPI", "0") != "0"
+
+
 class KernelTimer:
     """Brackets selected kernel launches with stream events (bench.py roofline):
     `records` collects (tag, start_event, stop_event, work) tuples."""
@@ -365,6 +372,76 @@ class KernelTimer:
 TIMER: KernelTimer | None = None
 
 
+class PendingProduct:
+    """A q_matmul product on the int16 MFMA route that has not been launched: the padded operands of
+    nqk_qgemm_i16 and, once `qmatmul` has it, the ZpTerm.  Its one consumer decides the launch:
+    `materialize` is nqk_qgemm_i16 (the int64 array), `dequantize` and `requantize` are
+    nqk_qgemm_i16_epi, which never writes that array.  All three are timed as "qgemm_i16"."""
+
+    dtype = np.dtype(np.int64)
+
+    def __init__(self, ap: DeviceArray, bt: DeviceArray, out_batch, M: int, N: int, K: int, kp: int, bmap):
+        self.ap, self.bt, self.bmap = ap, bt, bmap
+        self.shape = tuple(out_batch) + (M, N)
+        self.nb, self.M, self.N, self.K, self.kp = int(math.prod(out_batch)), M, N, K, kp
+        self.zp: ZpTerm | None = None
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+    def _timed(self, out_bytes: int, name: str, *args):
+        t0 = TIMER.begin() if TIMER is not None else None
+        _lib.call(name, *args)
+        if t0 is not None:  # one int8 MFMA product per pair of byte planes: 2 (int8 B) or 4
+            nb, M, N, K, wb = self.nb, self.M, self.N, self.K, self.bt.dtype.itemsize
+            TIMER.end("qgemm_i16", t0, (2 * nb * M * N * K * 2 * wb, nb * (2 * M * K + wb * N * K + out_bytes * M * N)))
+
+    def materialize(self) -> DeviceArray:
+        acc = DeviceArray(self.shape, np.int64)
+        M, N, kp = self.M, self.N, self.kp
+        self._timed(8, "nqk_qgemm_i16", self.ap.vp, self.bt.vp, self.bt.code, acc.vp, self.nb, M, N, kp, kp, kp, N,
+                    _lib.i64arr(self.bmap), M * kp, N * kp, M * N)
+        return acc
+
+    def _epilogue(self, out: DeviceArray, scale, **fields) -> None:
+        z = self.zp
+        e = _lib.Gemm16Epilogue(**fields)
+        if isinstance(scale, DeviceArray):
+            _check_cols(scale, self.N, "nqk_qgemm_i16_epi")
+            e.s_col = scale.ptr
+        else:
+            e.scale = float(np.float32(scale))
+        if z is not None:
+            e.zp_flags, e.zpa, e.zpb, e.zp_K = z.flags, z.zpa, z.zpb, z.K
+            e.row = z.row.ptr if z.row is not None else None
+            e.col = z.col.ptr if z.col is not None else None
+        M, N, kp = self.M, self.N, self.kp
+        self._timed(out.dtype.itemsize, "nqk_qgemm_i16_epi", self.ap.vp, self.bt.vp, self.bt.code, out.vp,
+                    _lib.NQK_F32 if out.dtype == np.float32 else out.code, self.nb, M, N, kp, kp, kp, N,
+                    _lib.i64arr(self.bmap), M * kp, N * kp, M * N, ctypes.byref(e))
+
+    def dequantize(self, scale) -> DeviceArray:
+        """`dequantize(self.materialize(), scale, self.zp)`, or `dequantize_cols` of a DeviceArray scale."""
+        out = DeviceArray(self.shape, np.float32)
+        self._epilogue(out, scale)
+        return out
+
+    def requantize(self, scale, bias: DeviceArray | None, res_scale, res_zp, bit_width: int) -> DeviceArray:
+        """`requantize(self.materialize(), scale, self.zp, bias, ...)` (`requantize_cols` of a DeviceArray
+        scale) at a bit width of 9..16, whose storage is int16."""
+        if not 9 <= bit_width <= 16:
+            raise ValueError(f"PendingProduct.requantize: bit width 9..16 (got {bit_width})")
+        if bias is not None and bias.size != self.N:
+            raise ValueError(f"bias of {bias.size} elements cannot broadcast over rows of {self.N}")
+        out = DeviceArray(self.shape, np.int16)
+        self._epilogue(out, scale, bias=bias.ptr if bias is not None else None,
+                       bias_dtype=bias.code if bias is not None else _lib.NQK_I64,
+                       res_scale=float(np.float32(res_scale)), res_zp=0 if res_zp is None else int(res_zp),
+                       has_res_zp=0 if res_zp is None else 1, bit_width=int(bit_width))
+        return out
+
+
 def _pad_k(x: DeviceArray, rows_shape, k: int, kp: int) -> DeviceArray:
     """Copy [..., rows, k] into a zero-filled [..., rows, kp] (kp % 16 == 0)."""
     out = DeviceArray(tuple(rows_shape) + (kp,), x.dtype).fill_zero()
@@ -374,12 +451,13 @@ def _pad_k(x: DeviceArray, rows_shape, k: int, kp: int) -> DeviceArray:
 
 
 def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray | None = None,
-            b_colsum: DeviceArray | None = None):
+            b_colsum: DeviceArray | None = None, defer: bool = False):
     """q_matmul (numpy_quantization.py:44-61): returns (acc, ZpTerm | None).
 
     a: [..., M, K] and b: [..., K, N] integer DeviceArrays (contiguous).  The int8
     path needs Bt[..., N, Kp]; `b_transposed` (and its column sums) may be passed in
-    pre-computed for constant weights.
+    pre-computed for constant weights.  With `defer`, a product of the int16 MFMA route comes
+    back as a PendingProduct (with NQK_GEMM16_EPI=1 only): the caller launches it with its consumer.
     """
     if a.ndim < 2 or b.ndim < 2:
         raise ValueError("q_matmul operands must have at least 2 dimensions")
@@ -415,20 +493,17 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
             copy_strided(b, bt, shape, src_st, contiguous_strides(b_batch + (N, kp)))
         else:
             bt = b_transposed
-        t0 = TIMER.begin() if TIMER is not None else None
         if use_i8:
+            t0 = TIMER.begin() if TIMER is not None else None
             acc = DeviceArray(out_batch + (M, N), np.int32)
             _lib.call("nqk_qgemm_i8", ap.vp, bt.vp, acc.vp, nb, M, N, kp, kp, kp, N, _lib.i64arr(bmap),
                       M * kp, N * kp, M * N)
             if t0 is not None:
                 TIMER.end("qgemm_i8", t0, (2 * nb * M * N * K, nb * (M * K + N * K + 4 * M * N)))
         else:
-            acc = DeviceArray(out_batch + (M, N), np.int64)
-            _lib.call("nqk_qgemm_i16", ap.vp, bt.vp, bt.code, acc.vp, nb, M, N, kp, kp, kp, N, _lib.i64arr(bmap),
-                      M * kp, N * kp, M * N)
-            if t0 is not None:  # one int8 MFMA product per pair of byte planes: 2 (int8 B) or 4
-                wb = bt.dtype.itemsize
-                TIMER.end("qgemm_i16", t0, (2 * nb * M * N * K * 2 * wb, nb * (2 * M * K + wb * N * K + 8 * M * N)))
+            acc = PendingProduct(ap, bt, out_batch, M, N, K, kp, bmap)
+            if not (defer and _gemm16_epi_enabled()):
+                acc = acc.materialize()
     else:
         acc = DeviceArray(out_batch + (M, N), np.int64)
         _lib.call("nqk_qgemm_generic", a.vp, a.code, b.vp, b.code, acc.vp, nb, M, N, K, K, 1, N, 1, N,
@@ -458,6 +533,8 @@ def qmatmul(a: DeviceArray, b: DeviceArray, zpa, zpb, b_transposed: DeviceArray 
         flags |= _lib.ZP_KCONST
     zt = ZpTerm(flags, 0 if zpa is None else int(zpa), 0 if zpb is None else int(zpb), K, row, col, bmap,
                 a_batch, b_batch, M, N)
+    if isinstance(acc, PendingProduct):
+        acc.zp = zt
     return acc, zt
 
 

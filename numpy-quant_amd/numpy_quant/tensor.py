@@ -234,11 +234,19 @@ class QTensor:
     `scale` may be a 1-D float32 vector (QModel.per_channel, not the reference's behaviour): one
     scale per index of the last axis, or, for a 2-D weight kept as a Gemm with transB stores it
     ([N][K]), of axis 0 (`scale_axis` = 0); its `.T` has the vector on the last axis again.
-    Such a tensor has no scalar zero point."""
+    Such a tensor has no scalar zero point.
+
+    With NQK_GEMM16_EPI=1 a q_matmul output on the int16 MFMA route starts as a `K.PendingProduct`: `dequantize` and
+    `requantize` launch the GEMM with their arithmetic as its epilogue (nqk_qgemm_i16_epi), and the
+    first read of `dev` launches the plain GEMM instead and keeps its int64 array."""
 
     def __init__(self, data: Union[np.ndarray, DeviceArray], bit_width: int, scale: np.float32,
                  zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None, scale_axis: int = -1):
-        if isinstance(data, DeviceArray):
+        self._pending = None  # the K.PendingProduct `dev` is made from on its first read
+        self._deq = None  # the FTensor of a pending product's fused dequantize (a value with two consumers)
+        if isinstance(data, K.PendingProduct):
+            self._dev, self._pending = None, data
+        elif isinstance(data, DeviceArray):
             if data.dtype.kind != "i":
                 raise ValueError("Use np.int64 for quantized tensors")
             self.dev = data
@@ -258,13 +266,14 @@ class QTensor:
         self.scale_axis = -1
         self._pc = None  # per-column scale: device copies of the vectors, shared with .T
         if K.is_cols(scale):
-            nd = self.dev.ndim
+            shp = tuple(self.shape)
+            nd = len(shp)
             ax = int(scale_axis) % nd if nd else 0
             if not isinstance(scale, np.ndarray) or scale.dtype != np.float32:
                 raise ValueError("Use a float32 ndarray for a per-column scale")
-            if nd == 0 or not (ax == nd - 1 or (nd == 2 and ax == 0)) or scale.shape[0] != self.dev.shape[ax]:
+            if nd == 0 or not (ax == nd - 1 or (nd == 2 and ax == 0)) or scale.shape[0] != shp[ax]:
                 raise ValueError(f"per-column scale of {scale.shape[0]} entries on axis {scale_axis} of a tensor of "
-                                 f"shape {tuple(self.dev.shape)}: the last axis (or axis 0 of a matrix) expected")
+                                 f"shape {shp}: the last axis (or axis 0 of a matrix) expected")
             if zero_point is not None and not isinstance(zero_point, K.ZpTerm):
                 raise ValueError("a per-column scale has no scalar zero point")
             self.scale_axis = -1 if ax == nd - 1 else 0
@@ -279,8 +288,23 @@ class QTensor:
         self._bt16 = None  # the same of a constant int16 weight (nqk_qgemm_i16's operand)
 
     @property
+    def dev(self) -> DeviceArray:
+        if self._dev is None:
+            self._dev = self._pending.materialize()
+        return self._dev
+
+    @dev.setter
+    def dev(self, data: DeviceArray):
+        self._dev = data
+
+    @property
+    def _unlaunched(self):
+        """The pending product while `dev` was never read, else None."""
+        return self._pending if self._dev is None else None
+
+    @property
     def shape(self):
-        return self.dev.shape
+        return self._pending.shape if self._dev is None else self._dev.shape
 
     @property
     def zero_point(self):
@@ -363,12 +387,17 @@ class QTensor:
         if isinstance(other, QTensor):
             if self._bias is not None:
                 raise ValueError("only one pending bias is supported")
-            return self._moved(self.dev, None, self._zero_point, bias=other)
+            return self._moved(self._unlaunched or self.dev, None, self._zero_point, bias=other)
         raise ValueError(f"Cannot add QTensor with {other.__class__}")
 
     def dequantize(self):
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
+        pend = self._unlaunched
+        if pend is not None and (self._pc is None or self.scale_axis == -1):
+            if self._deq is None:
+                self._deq = FTensor(pend.dequantize(self.scale if self._pc is None else self.scale_dev))
+            return self._deq
         if self._pc is not None:
             if self.scale_axis == 0:  # a transB Gemm weight [N][K]: through its transpose
                 return FTensor(permute(self.T.dequantize().dev, [1, 0]))
@@ -390,7 +419,10 @@ class QTensor:
         if self._bias is not None:
             bias = self._bias.dev
         rz = None if zero_point is None else int(zero_point)
-        if self._pc is not None:
+        pend = self._unlaunched
+        if pend is not None and 9 <= bit_width <= 16 and (self._pc is None or self.scale_axis == -1):
+            q = pend.requantize(self.scale if self._pc is None else self.scale_dev, bias, scale, rz, bit_width)
+        elif self._pc is not None:
             if self.scale_axis != -1:
                 raise ValueError("requantize: the per-column scale must lie on the last axis")
             q = K.requantize_cols(self.dev, self.scale_dev, self._zero_point, bias, scale, rz, bit_width)
@@ -424,7 +456,7 @@ class QTensor:
             raise ValueError("matmul: a per-column scale belongs to the right operand (the weight) only")
         if other._pc is not None and other.scale_axis != -1:
             raise ValueError("matmul: the weight's per-column scale must lie on its last axis (use .T)")
-        acc, zt = K.qmatmul(self.dev, other.dev, self.zp_scalar, other.zp_scalar, bt, col)
+        acc, zt = K.qmatmul(self.dev, other.dev, self.zp_scalar, other.zp_scalar, bt, col, defer=True)
         if other._pc is not None:
             # s[n] = f32(s_a) * f32(s_w[n]); the vector and its device copy are made once per s_a
             key = ("out", np.float32(self.scale).tobytes())

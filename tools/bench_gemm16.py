@@ -13,6 +13,15 @@ profiles/gemm16.json).
           without NQK_GEMM16=0, logits compared bit for bit
   error   model.compare's output MSE on the encoder-layer fixture at (8, 8), (16, 8), (16, 16)
 
+With --epi the steps are those of nqk_qgemm_i16_epi instead (e.g. --out profiles/gemm16_epi.json); the
+reference is the parent's route, which NQK_GEMM16_EPI=0 keeps:
+
+  epi_gemm   per product above: nqk_qgemm_i16 + nqk_dequantize (two launches, the int64 array between
+             them) against the one fused launch, compared bit for bit; the fused kernel alone gives
+             the bytes per second it achieves (operands read once + the f32 output)
+  epi_model  the node-loop forward of ViT-Base at (16, 8) and (16, 16), at --model-batch and at
+             --model-batch-large images, with and without NQK_GEMM16_EPI=0, logits compared bit for bit
+
 The legs of a step alternate in one process; a figure is the median of its --rounds windows,
 with min-max.  Each GPU step is a child process under its own time limit; after a step that
 fails or runs out of time nothing more is started.
@@ -138,6 +147,95 @@ def step_model(args) -> dict:
     return res
 
 
+EPI_LEGS = (("fused", "1"), ("two_launch", "0"))
+
+
+def step_epi_gemm(args) -> dict:
+    from numpy_quant import kernels as K
+    from numpy_quant.device import DeviceArray
+    rng = np.random.default_rng(16)
+    B, scale = args.gemm_batch, np.float32(3.1e-7)
+    res = {"gemm_batch": B}
+    for name, (heads, M, Kd, N, const) in SHAPES.items():
+        for wb, bdt in ((8, np.int8), (16, np.int16)):
+            if heads is None:
+                ash, bsh = (B * M, Kd), (Kd, N)
+            else:
+                ash, bsh = (B, heads, M, Kd), (B, heads, Kd, N)
+            a = DeviceArray.from_host(rng.integers(-32768, 32768, size=ash).astype(np.int16))
+            b = DeviceArray.from_host(rng.integers(np.iinfo(bdt).min, np.iinfo(bdt).max + 1, size=bsh).astype(bdt))
+            bt, col = K.weight_bt(b) if const else (None, None)
+
+            def call():  # what QTensor.matmul(...).dequantize() launches on either leg
+                acc = K.qmatmul(a, b, None, None, bt, col, defer=True)[0]
+                return acc.dequantize(scale) if isinstance(acc, K.PendingProduct) else K.dequantize(acc, scale, None)
+            outs = {}
+            for leg, env in EPI_LEGS:
+                os.environ["NQK_GEMM16_EPI"] = env
+                outs[leg] = call().to_host()
+            if outs["fused"].tobytes() != outs["two_launch"].tobytes():
+                raise AssertionError(f"{name} w{wb}: the fused launch and the two launches differ")
+            samples = {leg: [] for leg, _ in EPI_LEGS}
+            for i in range(args.warmup + args.rounds):
+                for leg, env in EPI_LEGS:
+                    os.environ["NQK_GEMM16_EPI"] = env
+                    ms = _timer_ms(lambda: [call() for _ in range(args.reps)]) / args.reps
+                    if i >= args.warmup:
+                        samples[leg].append(ms)
+            key = f"epi_{name}_a16w{wb}"
+            for leg, _ in EPI_LEGS:
+                res[f"{key}_{leg}_ms"], res[f"{key}_{leg}_ms_min_max"] = _stats(samples[leg])
+            res[f"{key}_speedup"] = round(res[f"{key}_two_launch_ms"] / res[f"{key}_fused_ms"], 2)
+            res[f"{key}_ranges_overlap"] = bool(max(samples["fused"]) >= min(samples["two_launch"]))
+            os.environ["NQK_GEMM16_EPI"] = "1"
+            K.TIMER = K.KernelTimer()
+            for _ in range(args.rounds):
+                call()
+            call().to_host()  # a synchronising call: every event has passed
+            recs = [r for r in K.TIMER.collect() if r[0] == "qgemm_i16"]
+            K.TIMER = None
+            ms = statistics.median(r[1] for r in recs)
+            res[f"{key}_kernel_ms"] = round(ms, 4)
+            res[f"{key}_kernel_bytes"] = int(recs[0][2][1])
+            res[f"{key}_kernel_tb_per_s"] = round(recs[0][2][1] / (ms * 1e-3) / 1e12, 3)
+    os.environ.pop("NQK_GEMM16_EPI", None)
+    return res
+
+
+def step_epi_model(args) -> dict:
+    from numpy_quant import onnx_proto
+    from numpy_quant.model import Model
+    res = {"model_batches": [args.model_batch, args.model_batch_large]}
+    for B in res["model_batches"]:
+        x = np.random.default_rng(12345).standard_normal((B, 3, 224, 224)).astype(np.float32)
+        proto = onnx_proto.load(os.path.join(MODELS, "vit_image_classifier_no_weights.onnx"), synthetic_weights=True)
+        onnx_proto.rebatch(proto, B)
+        model = Model.from_onnx(proto)
+        for wbw in (8, 16):
+            q = model.quantize([x], bit_width=16, weight_bit_width=wbw)
+            logits = {}
+            for leg, env in EPI_LEGS:
+                os.environ["NQK_GEMM16_EPI"] = env
+                logits[leg] = q([x])[0]
+            if logits["fused"].tobytes() != logits["two_launch"].tobytes():
+                raise AssertionError(f"(16, {wbw}) at {B} images: the two routes give different logits")
+            samples = {leg: [] for leg, _ in EPI_LEGS}
+            for i in range(args.warmup + args.rounds):
+                for leg, env in EPI_LEGS:
+                    os.environ["NQK_GEMM16_EPI"] = env
+                    ms = _timer_ms(lambda: q([x]))
+                    if i >= args.warmup:
+                        samples[leg].append(ms)
+            key = f"epi_model_b{B}_a16w{wbw}"
+            for leg, _ in EPI_LEGS:
+                res[f"{key}_{leg}_ms"], res[f"{key}_{leg}_ms_min_max"] = _stats(samples[leg], 2)
+            res[f"{key}_speedup"] = round(res[f"{key}_two_launch_ms"] / res[f"{key}_fused_ms"], 3)
+            res[f"{key}_ranges_overlap"] = bool(max(samples["fused"]) >= min(samples["two_launch"]))
+            del q
+    os.environ.pop("NQK_GEMM16_EPI", None)
+    return res
+
+
 def step_error(args) -> dict:
     from numpy_quant.model import Model
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -154,6 +252,7 @@ def step_error(args) -> dict:
 
 
 STEPS = {"gemm": (step_gemm, 300), "model": (step_model, 420), "error": (step_error, 240)}
+EPI_STEPS = {"epi_gemm": (step_epi_gemm, 300), "epi_model": (step_epi_model, 600)}
 
 
 def main(argv=None):
@@ -164,15 +263,19 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5, help="qmatmul calls per timed window")
     ap.add_argument("--out", help="also write the JSON line to this file")
-    ap.add_argument("--step", choices=sorted(STEPS), help="run one GPU step in this process (used by the parent)")
+    ap.add_argument("--model-batch-large", type=int, default=64, help="the second batch of --epi's forward")
+    ap.add_argument("--epi", action="store_true", help="measure nqk_qgemm_i16_epi against the two-launch route instead")
+    ap.add_argument("--step", choices=sorted({**STEPS, **EPI_STEPS}), help="run one GPU step in this process (used by the parent)")
     args = ap.parse_args(argv)
     if args.step:
-        print(json.dumps(STEPS[args.step][0](args)), flush=True)
+        print(json.dumps({**STEPS, **EPI_STEPS}[args.step][0](args)), flush=True)
         return 0
-    result = {"metric": "int16 activations on the int8 MFMAs (nqk_qgemm_i16) against nqk_qgemm_generic",
-              "rounds": args.rounds}
-    passthrough = [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("gemm_batch", "model_batch", "rounds", "warmup", "reps")]
-    for name, (_, limit) in STEPS.items():
+    metric = ("the fused dequantize / requantize epilogue (nqk_qgemm_i16_epi) against nqk_qgemm_i16 and a second launch"
+              if args.epi else "int16 activations on the int8 MFMAs (nqk_qgemm_i16) against nqk_qgemm_generic")
+    result = {"metric": metric, "rounds": args.rounds}
+    passthrough = [f"--{k.replace('_', '-')}={getattr(args, k)}"
+                   for k in ("gemm_batch", "model_batch", "model_batch_large", "rounds", "warmup", "reps")]
+    for name, (_, limit) in (EPI_STEPS if args.epi else STEPS).items():
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name] + passthrough
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=limit)
