@@ -258,6 +258,26 @@ int nqk_qgemm_i16_epi(const int16_t* a, const void* bt, int bt_dtype, void* out,
                       int64_t ldo, const int64_t* bmap, int64_t a_mat_stride, int64_t b_mat_stride,
                       int64_t out_mat_stride, const nqk_gemm16_epilogue* params);
 
+/* int8 MFMA GEMM for a weight with one scale per group of g consecutive k and column
+ * (Model.quantize(group_size=g)); G = K / g.  a [M][lda] and bt [N][ldb] int8 as nqk_qgemm_i8 takes
+ * them (a batch is folded into M: the weight is 2-D), sg [G][N] float32 = f32(f32(s_a) * S[j][n]),
+ * gsum [G][N] int32 = the per-group column sums of the weight (nqk_group_colsum).  Per output
+ *   P_j = sum_{k in group j} a[m][k] bt[n][k] - zpa gsum[j][n]            (int32, exact)
+ *   acc = 0.0 (f64);  acc = acc + f64(sg[j][n]) * f64(P_j)  for j = 0 .. G - 1 in that order
+ *   out[m][n] = f32(acc)                                                  (out [M][ldo] float32)
+ * f64(sg) * f64(P_j) is exact (24 + at most 29 bits), so the only roundings are the G - 1 f64
+ * additions and the f32 conversion; with G = 1 this is nqk_dequantize_cols of nqk_qgemm_i8's
+ * result.  No integer [M][N] array is written.  Without a zero point (has_zpa = 0) gsum may be
+ * NULL.  Refused before any launch: g no positive multiple of 32 or above 16384, K no positive
+ * multiple of g, lda / ldb no multiple of 16 or shorter than K, ldo < N, NULL or misaligned
+ * pointers (a, bt 16 bytes; sg, gsum, out 4), zpa outside -128..127, more than 2^31 - 1 tiles. */
+int nqk_qgemm_group(const int8_t* a, const int8_t* bt, const float* sg, const int32_t* gsum, float* out,
+                    int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldo, int64_t g,
+                    int64_t zpa, int has_zpa);
+/* gsum[j][n] = sum_{k in group j} bt[n][k], int32 [K / g][N]; once per constant weight.  Refuses
+ * what nqk_qgemm_group refuses of bt, N, K, ldb and g, and a NULL or misaligned gsum. */
+int nqk_group_colsum(const int8_t* bt, int64_t N, int64_t K, int64_t ldb, int64_t g, int32_t* gsum);
+
 /* ------------------------------------------- float32 GEMM (BLAS-order exact) */
 /* C = A[M][K] . B[K][N] (element strides a_sm/a_sk, b_sk/b_sn).  Every output element is the
  * reference BLAS's summation: K is cut into OpenBLAS level-3 blocks (GEMM_Q=448

@@ -36,6 +36,11 @@ inline BatchMap batch_map(const int64_t* p) {
 __host__ __device__ inline int64_t map_a(const BatchMap& m, int64_t b) { return (b / m.inner) * m.ao + (b % m.inner) * m.ai; }
 __host__ __device__ inline int64_t map_b(const BatchMap& m, int64_t b) { return (b / m.inner) * m.bo + (b % m.inner) * m.bi; }
 
+// Byte offset of 16-byte chunk `chunk` of row `row` in an int8 operand tile of 64-byte LDS rows
+// (k_qgemm_i8, k_qgemm_i16, k_qgemm_group): chunk c of row r sits at c ^ ((r >> 2) & 3), so that
+// every ds_read_b128 lane group touches 16 distinct 16-byte bank slots
+__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
+
 // typed load/store of the integer storage classes
 template <typename T> struct DT;
 template <> struct DT<int8_t>  { static constexpr int code = NQK_I8; };

@@ -31,8 +31,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 // that every ds_read_b128 lane group touches 16 distinct 16-B bank slots.
 constexpr int BM = 128, BN = 128, BK = 64;
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
 __global__ void __launch_bounds__(256)
 k_qgemm_i8(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, int32_t* __restrict__ C,
            int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, BatchMap bm,

@@ -50,8 +50,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int PLANE = BM * BK;  // bytes of one int8 plane tile (BM == BN)
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
 __device__ __forceinline__ int dot_ones(const v4i& c, int s) {
   s = __builtin_amdgcn_sdot4(c[0], 0x01010101, s, false);
   s = __builtin_amdgcn_sdot4(c[1], 0x01010101, s, false);

@@ -109,6 +109,8 @@ SIGNATURES = {
     "nqk_qgemm_i16": [_p, _p, _i, _p, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l],
     "nqk_qgemm_i16_epi": [_p, _p, _i, _p, _i, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l,
                           ctypes.POINTER(Gemm16Epilogue)],
+    "nqk_qgemm_group": [_p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _i],
+    "nqk_group_colsum": [_p, _l, _l, _l, _l, _p],
     "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l, _l, _l],
     "nqk_sgemv_t": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_sgemv_small": [_p, _p, _p, _l, _l, _l],

@@ -89,6 +89,9 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
     constant of `qmodel` (device-to-device copies, no host round trip)."""
     from .model import Constant
     from .tensor import QTensor
+    if getattr(qmodel, "group_size", None) is not None:
+        raise ValueError("blob: a model with group-wise weight scales (group_size) cannot be saved: no blob "
+                         "version holds the [G, N] scale arrays yet")
     consts = []
     off = 0
     for v in qmodel.values:

@@ -162,18 +162,21 @@ class Comparator:
         """Accumulate `got` (the quantized model's FTensor or QTensor) against `ref` (the float
         model's FTensor) under `name`: one call of the kernel, no synchronisation, no download.
         A QTensor is read in its integer storage when its zero point is a scalar or None; one
-        with a q_matmul zero-point term or a per-column scale goes through `dequantize()` first, and one with a
+        with a q_matmul zero-point term, a per-column scale or group-wise scales goes through `dequantize()` first, and one with a
         pending bias raises what `dequantize()` raises."""
         if not isinstance(ref, FTensor):
             raise ValueError(f"{name}: the reference side must be an FTensor (got {type(ref).__name__})")
         if not isinstance(got, (FTensor, QTensor)):
             raise ValueError(f"{name}: the compared side must be an FTensor or a QTensor (got {type(got).__name__})")
-        if tuple(ref.dev.shape) != tuple(got.dev.shape):
-            raise ValueError(f"{name}: shapes differ (float model {tuple(ref.dev.shape)}, quantized model "
-                             f"{tuple(got.dev.shape)})")
+        grouped = isinstance(got, QTensor) and (got.group_size is not None or
+                                                isinstance(got._unlaunched, K.GroupProduct))
+        shape = tuple(got.shape) if isinstance(got, QTensor) else tuple(got.dev.shape)
+        if tuple(ref.dev.shape) != shape:
+            raise ValueError(f"{name}: shapes differ (float model {tuple(ref.dev.shape)}, quantized model {shape})")
         scale = zp = None
         if isinstance(got, QTensor):
-            if got._bias is not None or isinstance(got._zero_point, K.ZpTerm) or got.per_column:
+            # group-wise scales: a weight through its own dequantize(), a product through nqk_qgemm_group
+            if grouped or got._bias is not None or isinstance(got._zero_point, K.ZpTerm) or got.per_column:
                 y = got.dequantize().dev  # nqk_compare_stats takes one scalar scale
             else:
                 y, scale, zp = got.dev, got.scale, got._zero_point

@@ -554,6 +554,70 @@ def weight_bt(b: DeviceArray):
     return bt, col
 
 
+# ----------------------------------------------------------------------------- group-wise weight scales
+def check_group_size(group_size) -> int:
+    """`group_size` as an int: a positive multiple of 32, at most 16384 (nqk_qgemm_group's range)."""
+    if (isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or group_size < 32
+            or group_size % 32 or group_size > 16384):
+        raise ValueError(f"group_size must be a positive multiple of 32, at most 16384 (got {group_size!r})")
+    return int(group_size)
+
+
+def group_colsum(bt: DeviceArray, g: int) -> DeviceArray:
+    """int32 [K / g, N]: the sums of int8 `bt` [N, K] (weight_bt's image) over every group of g
+    consecutive k (nqk_group_colsum); once per constant weight."""
+    g = check_group_size(g)
+    if bt.dtype != np.int8 or bt.ndim != 2 or bt.shape[1] % g:
+        raise ValueError(f"group_colsum: int8 [N, K] with K a multiple of {g} expected (got {bt.dtype} {bt.shape})")
+    N, K = bt.shape
+    gsum = DeviceArray((K // g, N), np.int32)
+    _lib.call("nqk_group_colsum", bt.vp, N, K, K, g, gsum.vp)
+    return gsum
+
+
+def qmatmul_group(a: DeviceArray, bt: DeviceArray, gsum: DeviceArray | None, sg: DeviceArray, zpa, g: int) -> DeviceArray:
+    """float32 [..., M, N] of int8 `a` [..., M, K] times the grouped weight `bt` [N, K] (nqk_qgemm_group,
+    include/nqk.h: the arithmetic): `sg` float32 [K / g, N] the products f32(s_a * S), `gsum` the
+    weight's group_colsum (needed with a zero point `zpa`; None without).  The batch axes of `a` are
+    folded into M.  Timed as "qgemm_group"."""
+    g = check_group_size(g)
+    if a.dtype != np.int8 or bt.dtype != np.int8 or a.ndim < 2 or bt.ndim != 2:
+        raise ValueError("qmatmul_group: int8 a [..., M, K] and int8 bt [N, K] expected")
+    N, K = bt.shape
+    if a.shape[-1] != K or K % g:
+        raise ValueError(f"qmatmul_group: K of a ({a.shape[-1]}) and of bt ({K}) must agree and be a multiple of {g}")
+    G = K // g
+    if sg.dtype != np.float32 or sg.shape != (G, N):
+        raise ValueError(f"qmatmul_group: sg must be float32 [{G}, {N}]")
+    if zpa is not None and (gsum is None or gsum.dtype != np.int32 or gsum.shape != (G, N)):
+        raise ValueError(f"qmatmul_group: a zero point needs gsum, int32 [{G}, {N}]")
+    M = a.size // K
+    out = DeviceArray(a.shape[:-1] + (N,), np.float32)
+    t0 = TIMER.begin() if TIMER is not None else None
+    _lib.call("nqk_qgemm_group", a.vp, bt.vp, sg.vp, gsum.vp if zpa is not None else None, out.vp, M, N, K, K, K, N, g,
+              0 if zpa is None else int(zpa), 0 if zpa is None else 1)
+    if t0 is not None:
+        TIMER.end("qgemm_group", t0, (2 * M * N * K, M * K + N * K + 4 * M * N + (4 if zpa is None else 8) * G * N))
+    return out
+
+
+class GroupProduct:
+    """A product with a group-wise scaled weight that has not been launched: the operands of
+    nqk_qgemm_group.  PendingProduct's counterpart, with one consumer: `dequantize`.  No integer
+    accumulator exists for it, since every group's partial sum is rescaled inside the k loop."""
+
+    def __init__(self, a: DeviceArray, bt: DeviceArray, gsum: DeviceArray, sg: DeviceArray, zpa, g: int):
+        self.a, self.bt, self.gsum, self.sg, self.zpa, self.g = a, bt, gsum, sg, zpa, g
+        self.shape = tuple(a.shape[:-1]) + (bt.shape[0],)
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+    def dequantize(self) -> DeviceArray:
+        return qmatmul_group(self.a, self.bt, self.gsum, self.sg, self.zpa, self.g)
+
+
 # ----------------------------------------------------------------------------- float GEMM
 def sgemm(a: DeviceArray, a_sm, a_sk, b: DeviceArray, b_sk, b_sn, M, N, K, batch=1, bmap=None,
           a_ms=0, b_ms=0, transb=False) -> DeviceArray:

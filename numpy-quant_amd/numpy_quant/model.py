@@ -25,7 +25,8 @@ from . import onnx_proto
 from .device import DeviceArray, permute, sync
 from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
-from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, qconv2d, quantize_tensor, where)
+from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, group_scales, qconv2d, quantize_tensor,
+                     where)
 from . import kernels as K
 
 
@@ -87,7 +88,10 @@ def _is_image_list(array, pre) -> bool:
 
 def _topk_output(tensor, k: int):
     """(indices [B, k], probabilities [B, k]) device tensors of a model output [..., classes],
-    leading axes flattened into B.  A QTensor is read as it is: no float logits are made."""
+    leading axes flattened into B.  A QTensor is read as it is: no float logits are made (but for a
+    product with group-wise weight scales, which only its dequantize() reads)."""
+    if isinstance(tensor, QTensor) and isinstance(tensor._unlaunched, K.GroupProduct):
+        tensor = tensor.dequantize()
     if not isinstance(tensor, (FTensor, QTensor)) or tensor.dev.ndim < 2:
         shape = tuple(tensor.dev.shape) if hasattr(tensor, "dev") else np.shape(getattr(tensor, "data", None))
         raise ValueError(f"classify: the model's first output must be [batch, classes] (got {type(tensor).__name__} "
@@ -256,6 +260,29 @@ def per_channel_axis(value):
             return None
         axes.add(0 if node.op == "Gemm" and node.attrs.get("transB") else 1)
     return axes.pop() if len(axes) == 1 else None
+
+
+def group_eligible(value, group_size: int) -> bool:
+    """Whether a constant takes group-wise scales (QModel.group_size): a 2-D float constant [K, N]
+    consumed only as input 1 of MatMul nodes, with K a multiple of `group_size`.  A Gemm weight is
+    not (its bias is quantized with s_x * s_w[n], which a grouped weight does not have), nor is a
+    weight whose K the group does not divide: those follow the other flags."""
+    if per_channel_axis(value) != 1 or any(node.op != "MatMul" for node in value.outputs):
+        return False
+    return value.data.dev.shape[0] % group_size == 0
+
+
+def check_group_args(group_size, bit_width, weight_clip):
+    """`group_size` as Model.quantize takes it: None, or a positive multiple of 32 (at most 16384)
+    beside a bit_width of at most 8 (the 16-bit route is not grouped) and no weight_clip."""
+    if group_size is None:
+        return None
+    group_size = K.check_group_size(group_size)
+    if bit_width > 8:
+        raise ValueError(f"group_size needs bit_width <= 8: the int16 activation route is not grouped (got {bit_width})")
+    if weight_clip is not None:
+        raise ValueError("group_size does not combine with weight_clip: the clipping search is per tensor or per column")
+    return group_size
 
 
 def column_scales(tensor: FTensor, axis: int, bit_width: int) -> np.ndarray:
@@ -474,7 +501,7 @@ class Model:
         return equalize(self, batches, alpha, emax, pow2)
 
     def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
         (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
@@ -484,9 +511,14 @@ class Model:
         `weight_clip="mse"` (not the reference's behaviour either): the scale of each of the same
         weights, per tensor or per column, is shrunk by the ratio 1 - 0.5 g / clip_steps, g <
         clip_steps <= 64, that quantizes the weight with the smallest squared error, searched on the
-        device (QModel.weight_clip); g = 0 is the scale without the search."""
+        device (QModel.weight_clip); g = 0 is the scale without the search.
+        `group_size=g` (not the reference's behaviour either; a multiple of 32, bit_width <= 8, no
+        weight_clip): every MatMul weight [K, N] with K a multiple of g gets one scale per group of
+        g consecutive k and column, at the weights' width (QModel.group_size); its products run
+        nqk_qgemm_group.  Every other weight follows the other flags."""
         # refused before the calibration forward
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
+        check_group_args(group_size, bit_width, weight_clip)
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool, bw=bit_width):
@@ -494,7 +526,8 @@ class Model:
             return QuantizationParams(s, z)
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
-                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps)
+                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
+                             group_size=group_size)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -516,12 +549,14 @@ class Model:
         return cal.ranges()
 
     def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
-                        per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64):
+                        per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
         `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
         and maxima of the constants.  So is `weight_clip` with `clip_weights`: two clippers of the
-        same constants."""
+        same constants.  `group_size` as `quantize` takes it; the group ranges are the exact minima
+        and maxima of the constants, whatever `clip_weights` says."""
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
+        check_group_args(group_size, bit_width, weight_clip)
         if weight_clip is not None and clip_weights:
             raise ValueError("quantize_stream: weight_clip searches the scales of the weights; clip_weights does "
                              "not combine with it")
@@ -535,7 +570,8 @@ class Model:
             return QuantizationParams(s, z)
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
-                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps)
+                             weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
+                             group_size=group_size)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -611,7 +647,7 @@ class Model:
         return blob.load(self, path)
 
     def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here.
         `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
@@ -622,9 +658,12 @@ class Model:
         that width.
         `weight_clip="mse"`: the scale of every eligible weight, computed here at its width, goes
         through the clipping search (searched_scale) with `clip_steps` candidates; given scales are
-        taken as they are."""
+        taken as they are.
+        `group_size`: eligible MatMul weights (group_eligible) get the scales [K / g, N] of their
+        groups (tensor.group_scales) at the weights' width, whatever `per_channel` says."""
         wbw = weight_width(bit_width, weight_bit_width)
         ratios = clip_candidates(weight_clip, clip_steps, wbw)
+        group_size = check_group_args(group_size, bit_width, weight_clip)
         constants = constants or {}
         wanted = {}
         if constants:
@@ -663,6 +702,13 @@ class Model:
             if isinstance(value, Constant):
                 # the constant's width: the weights' for a MatMul / Gemm weight, else the model's
                 cbw = wbw if wbw != bit_width and per_channel_axis(value) is not None else bit_width
+                if group_size is not None and value.name not in constants and group_eligible(value, group_size):
+                    p = QuantizationParams(group_scales(value.data, group_size, cbw), None)
+                    qt = quantize_tensor(value.data, cbw, p.scale, None)
+                    qt._is_weight = True
+                    qvalues[value.name] = Constant(value.name, [], qt)
+                    qp[value.name] = p
+                    continue
                 p = params(value, False) if cbw == bit_width else params(value, False, cbw)
                 axis = per_channel_axis(value) if per_channel else None
                 if axis is not None and not given:
@@ -746,6 +792,7 @@ class Model:
         qmodel.per_channel = bool(per_channel)
         qmodel.weight_bit_width = wbw
         qmodel.weight_clip = weight_clip
+        qmodel.group_size = group_size
         return qmodel
 
 
@@ -784,6 +831,12 @@ class QModel(Model):
         # of the clipping search of Model.quantize(weight_clip="mse"), else None.  A record only:
         # quant_params holds the chosen scales, and nothing downstream reads this.
         self.weight_clip = None
+        # opt-in, not the reference's behaviour: the group size g of Model.quantize(group_size=g), else
+        # None.  Every MatMul weight [K, N] with K a multiple of g (group_eligible) carries scales
+        # [K / g, N] in quant_params, one per group of g consecutive k and column; its products are
+        # nqk_qgemm_group's float32 results (tensor.QTensor on a K.GroupProduct), which have no integer
+        # accumulator.  Such a model runs the node loop: the plan claims none of its layers.
+        self.group_size = None
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "

@@ -1266,7 +1266,9 @@ class Plan:
                 continue
             claimed[lg.ln] = claimed[lg.g] = lg
             self.pushdowns += 1
-        if qmodel.bit_width <= 8 and qmodel.bit_width >= 2:
+        # group-wise weight scales (QModel.group_size): the fused GEMMs scale once per column, so
+        # such a model's layers stay in the node loop (nqk_qgemm_group)
+        if qmodel.bit_width <= 8 and qmodel.bit_width >= 2 and getattr(qmodel, "group_size", None) is None:
             for node in qmodel.nodes:
                 if node.op != "LayerNormalization" or node in claimed:
                     continue

@@ -238,13 +238,19 @@ class QTensor:
 
     With NQK_GEMM16_EPI=1 a q_matmul output on the int16 MFMA route starts as a `K.PendingProduct`: `dequantize` and
     `requantize` launch the GEMM with their arithmetic as its epilogue (nqk_qgemm_i16_epi), and the
-    first read of `dev` launches the plain GEMM instead and keeps its int64 array."""
+    first read of `dev` launches the plain GEMM instead and keeps its int64 array.
+
+    `scale` may also be a 2-D float32 array [G, N] on a 2-D weight [K, N] (QModel.group_size): one
+    scale per group of `group_size` = K / G consecutive k and column, no zero point.  `x.matmul(w)`
+    of such a weight is a QTensor on a `K.GroupProduct` whose scale is f32(s_x * scale): only
+    `dequantize()` reads it (nqk_qgemm_group rescales every group inside its k loop), and whatever
+    needs the integer accumulator raises ValueError."""
 
     def __init__(self, data: Union[np.ndarray, DeviceArray], bit_width: int, scale: np.float32,
                  zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None, scale_axis: int = -1):
         self._pending = None  # the K.PendingProduct `dev` is made from on its first read
         self._deq = None  # the FTensor of a pending product's fused dequantize (a value with two consumers)
-        if isinstance(data, K.PendingProduct):
+        if isinstance(data, (K.PendingProduct, K.GroupProduct)):
             self._dev, self._pending = None, data
         elif isinstance(data, DeviceArray):
             if data.dtype.kind != "i":
@@ -265,6 +271,8 @@ class QTensor:
                 raise ValueError("array zero points are only produced by q_matmul (ZpTerm)")
         self.scale_axis = -1
         self._pc = None  # per-column scale: device copies of the vectors, shared with .T
+        self.group_size = None  # of a weight with group-wise scales [G, N]
+        self._gs = None  # such a weight's caches: "dev" (the scales), "op" (Bt, gsum), per s_a the products sg
         if K.is_cols(scale):
             shp = tuple(self.shape)
             nd = len(shp)
@@ -278,8 +286,19 @@ class QTensor:
                 raise ValueError("a per-column scale has no scalar zero point")
             self.scale_axis = -1 if ax == nd - 1 else 0
             self._pc = {}
-        elif np.ndim(scale) > 1:
-            raise ValueError("a scale is a scalar or a 1-D vector")
+        elif np.ndim(scale) == 2 and not isinstance(data, K.GroupProduct):
+            shp = tuple(self.shape)
+            if not isinstance(scale, np.ndarray) or scale.dtype != np.float32:
+                raise ValueError("Use a float32 ndarray for group-wise scales")
+            if len(shp) != 2 or scale.shape[1] != shp[1] or scale.shape[0] < 1 or shp[0] % scale.shape[0]:
+                raise ValueError(f"group-wise scales {scale.shape} on a tensor of shape {shp}: [G, N] on a weight "
+                                 "[K, N] with K a multiple of G expected")
+            if zero_point is not None:
+                raise ValueError("group-wise scales have no zero point")
+            self.group_size = K.check_group_size(shp[0] // scale.shape[0])
+            self._gs = {}
+        elif np.ndim(scale) > 1 and not isinstance(data, K.GroupProduct):
+            raise ValueError("a scale is a scalar, a 1-D vector or a [G, N] array of group-wise scales")
         self.bit_width = bit_width
         self.scale = scale
         self._zero_point = zero_point
@@ -287,9 +306,15 @@ class QTensor:
         self._bt = None  # cached (Bt, colsum) when this is a constant int8 weight
         self._bt16 = None  # the same of a constant int16 weight (nqk_qgemm_i16's operand)
 
+    def _needs_accumulator(self, what: str) -> None:
+        if isinstance(self._pending, K.GroupProduct):
+            raise ValueError(f"{what}: a product with group-wise weight scales has no integer accumulator (every "
+                             "group is rescaled inside the GEMM); only dequantize() reads it")
+
     @property
     def dev(self) -> DeviceArray:
         if self._dev is None:
+            self._needs_accumulator("dev")
             self._dev = self._pending.materialize()
         return self._dev
 
@@ -362,6 +387,9 @@ class QTensor:
 
     @property
     def T(self):
+        self._needs_accumulator("T")
+        if self.group_size is not None:
+            raise ValueError("transpose of a weight with group-wise scales is not supported")
         if isinstance(self._zero_point, K.ZpTerm) or self._bias is not None:
             raise ValueError("transpose of a q_matmul output is not on the QModel path")
         perm = list(range(self.dev.ndim))[::-1]
@@ -371,6 +399,8 @@ class QTensor:
         return out
 
     def reshape(self, shape: ITensor):
+        if self.group_size is not None:
+            raise ValueError("reshape of a weight with group-wise scales is not supported")
         tgt = _reshape_target(self.dev.shape, shape.data)
         if self._pc is not None and (self.scale_axis != -1 or not tgt or tgt[-1] != self.dev.shape[-1]):
             raise ValueError(f"reshape of a tensor with a per-column scale must keep its last axis "
@@ -379,12 +409,15 @@ class QTensor:
 
     def transpose(self, *axes):
         perm = axes[0] if len(axes) == 1 and not isinstance(axes[0], int) else axes
+        if self.group_size is not None:
+            raise ValueError("transpose of a weight with group-wise scales is not supported")
         if self._pc is not None and (isinstance(self._zero_point, K.ZpTerm) or self._bias is not None):
             raise ValueError("transpose of a q_matmul output with a per-column scale is not supported")
         return self._moved(permute(self.dev, list(perm)), list(perm), self._zero_point)
 
     def __add__(self, other: "QTensor"):
         if isinstance(other, QTensor):
+            self._needs_accumulator("__add__")
             if self._bias is not None:
                 raise ValueError("only one pending bias is supported")
             return self._moved(self._unlaunched or self.dev, None, self._zero_point, bias=other)
@@ -394,6 +427,13 @@ class QTensor:
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
         pend = self._unlaunched
+        if isinstance(pend, K.GroupProduct):
+            if self._deq is None:
+                self._deq = FTensor(pend.dequantize())
+            return self._deq
+        if self.group_size is not None:  # a weight: per-column dequantize on the [g, G N] view
+            q = _group_view(self.dev, self.group_size)
+            return FTensor(_group_unview(K.dequantize_cols(q, self.group_scale_dev, None), self.dev.shape))
         if pend is not None and (self._pc is None or self.scale_axis == -1):
             if self._deq is None:
                 self._deq = FTensor(pend.dequantize(self.scale if self._pc is None else self.scale_dev))
@@ -409,12 +449,14 @@ class QTensor:
         integer storage as it reads it."""
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
+        self._needs_accumulator("topk")
         if self._pc is not None:  # the top-k kernel dequantizes with one scalar scale
             return self.dequantize().topk(k)
         idx, prob, _ = K.topk_softmax(self.dev, k, scale=self.scale, zp=self._zero_point)
         return DeviceITensor(idx), FTensor(prob)
 
     def requantize(self, bit_width: int, scale: np.float32, zero_point):
+        self._needs_accumulator("requantize")
         bias = None
         if self._bias is not None:
             bias = self._bias.dev
@@ -429,6 +471,38 @@ class QTensor:
         else:
             q = K.requantize(self.dev, self.scale, self._zero_point, bias, scale, rz, bit_width)
         return QTensor(q, bit_width, scale, zero_point)
+
+    @property
+    def group_scale_dev(self) -> DeviceArray:
+        """The group-wise scales as the float32 vector [G N] of the [g, G N] view (uploaded once)."""
+        d = self._gs.get("dev")
+        if d is None:
+            d = self._gs["dev"] = DeviceArray.from_host(np.ascontiguousarray(self.scale, dtype=np.float32).ravel())
+        return d
+
+    def group_operand(self):
+        """(Bt, gsum) of a constant int8 weight with group-wise scales, computed once."""
+        op = self._gs.get("op")
+        if op is None:
+            bt, _ = self.weight_operand()
+            op = self._gs["op"] = (bt, K.group_colsum(bt, self.group_size))
+        return op
+
+    def _matmul_group(self, other: "QTensor"):
+        """self [.., M, K] times a weight with group-wise scales: sg = f32(f32(s_a) * S), it and its
+        device copy made once per s_a (as `_pc` keeps the per-column products)."""
+        if self._pc is not None or self.group_size is not None or np.ndim(self.scale):
+            raise ValueError("matmul: group-wise scales belong to the right operand (the weight) only")
+        if self.dev.dtype != np.int8 or other.dev.dtype != np.int8:
+            raise ValueError("matmul: a weight with group-wise scales multiplies int8 operands (bit widths <= 8)")
+        bt, gsum = other.group_operand()
+        key = ("out", np.float32(self.scale).tobytes())
+        hit = other._gs.get(key)
+        if hit is None:
+            sg = (np.float32(self.scale) * other.scale).astype(np.float32)
+            hit = other._gs[key] = (sg, DeviceArray.from_host(sg))
+        prod = K.GroupProduct(self.dev, bt, gsum, hit[1], self.zp_scalar, other.group_size)
+        return QTensor(prod, 4 * self.bit_width, hit[0], None)
 
     def weight_operand(self):
         """(Bt, colsum) of a constant int8 or int16 weight, computed once."""
@@ -446,6 +520,8 @@ class QTensor:
         narrow_w = ((getattr(other, "_is_weight", False) or getattr(other, "_of_weight", False))
                     and other.bit_width <= self.bit_width)
         assert narrow_w or self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
+        if other.group_size is not None:
+            return self._matmul_group(other)
         bt = col = None
         if other._bt is not None or other._bt16 is not None or getattr(other, "_is_weight", False):
             # an int16 weight only beside an int16 activation (nqk_qgemm_i16); a wider one never
@@ -499,10 +575,48 @@ class QTensor:
 Tensor = Union[ITensor, FTensor, QTensor]
 
 
+def _group_view(x: DeviceArray, g: int) -> DeviceArray:
+    """[K, N] as [g, G N]: column j N + n holds the g elements of group j of column n."""
+    k, n = x.shape
+    return permute(x.reshape((k // g, g, n)), [1, 0, 2]).reshape((g, (k // g) * n))
+
+
+def _group_unview(x: DeviceArray, shape) -> DeviceArray:
+    k, n = shape
+    g = x.shape[0]
+    return permute(x.reshape((g, k // g, n)), [1, 0, 2]).reshape((k, n))
+
+
+def group_scales(tensor: "FTensor", g: int, bit_width: int) -> np.ndarray:
+    """float32 [K / g, N]: quant_parameters (symmetric) of the range, clamped to include 0, of every
+    group of g consecutive k of every column of the 2-D `tensor` [K, N]: column_scales' rule on the
+    [g, G N] view, the minima and maxima from one kernel.  quant_parameters' float32 arithmetic
+    element by element: (2 * max(hi, lo)) / (2^bw - 1)."""
+    k, n = tensor.dev.shape
+    mn, mx = K.minmax_cols(_group_view(tensor.dev, g))
+    zero = np.float32(0.0)
+    lo, hi = np.minimum(mn, zero), np.maximum(mx, zero)
+    qlo, qhi = -(2.0 ** (bit_width - 1)), 2.0 ** (bit_width - 1) - 1.0
+    return ((2 * np.maximum(hi, lo)) / (qhi - qlo)).astype(np.float32).reshape(k // g, n)
+
+
 def quantize_tensor(tensor: FTensor, bit_width: int, scale: np.float32, zero_point, scale_axis: int = -1):
     """tensor.py:299-301 on device.  A 1-D float32 `scale` (QModel.per_channel) quantizes every
     element with the scale of its index on the last axis, or on axis 0 of a matrix
     (`scale_axis` = 0: a Gemm weight stored for transB); it takes no zero point."""
+    if np.ndim(scale) == 2:  # group-wise scales [G, N] of a weight [K, N]: quantize_cols on the [g, G N] view
+        if zero_point is not None:
+            raise ValueError("group-wise scales take no zero point")
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        if tensor.dev.ndim != 2 or scale.shape[1] != tensor.dev.shape[1] or tensor.dev.shape[0] % scale.shape[0]:
+            raise ValueError(f"group-wise scales {scale.shape} do not fit a weight of shape {tuple(tensor.dev.shape)}")
+        k, n = tensor.dev.shape
+        g = K.check_group_size(k // scale.shape[0])
+        sdev = DeviceArray.from_host(scale.ravel())
+        q = _group_unview(K.quantize_cols(_group_view(tensor.dev, g), bit_width, sdev), (k, n))
+        out = QTensor(q, bit_width, scale=scale, zero_point=None)
+        out._gs["dev"] = sdev
+        return out
     if K.is_cols(scale):
         if zero_point is not None:
             raise ValueError("a per-column scale takes no zero point")
