@@ -278,6 +278,42 @@ int nqk_qgemm_group(const int8_t* a, const int8_t* bt, const float* sg, const in
  * what nqk_qgemm_group refuses of bt, N, K, ldb and g, and a NULL or misaligned gsum. */
 int nqk_group_colsum(const int8_t* bt, int64_t N, int64_t K, int64_t ldb, int64_t g, int32_t* gsum);
 
+/* Per-token (per-row) activation quantization (Model.quantize(per_token=True)): every row of the
+ * left operand of a MatMul with a constant weight takes the scale and zero point of its own range
+ * when it is quantized; nothing is calibrated.  Row m of x [rows][ldx] float32, cols columns used:
+ *   lo = min(min_k x[m][k], 0),  hi = max(max_k x[m][k], 0)
+ *   (s[m], z[m]) = quant_parameters(lo, hi, bit_width, asymmetric): in float32,
+ *       s = (hi - lo) / (2^bw - 1),  z = rint(qlo - lo / s),  qlo = -2^(bw-1), qhi = 2^(bw-1) - 1
+ *     (0 lies in the range, so z lies in qlo..qhi)
+ *   a row whose float32 s is 0 (all zeros, or a range that underflows) is degenerate:
+ *     s[m] = 1, z[m] = 0 and every q = 0.  This is not the reference's behaviour, which divides 0 by 0.
+ *   q[m][k] = int(rint(clip(f64(z[m]) + f64(f32(x[m][k] / s[m])), qlo, qhi)))
+ *     (nqk_quantize's has_zp formula with the row's parameters; IEEE divide, ties to even)
+ * q [rows][ldq] int8 at every bit width 2..8, s [rows] float32, z [rows] int32.  The bytes of
+ * columns cols .. ldq - 1 are written as 0: with ldq = cols rounded up to 16, q is nqk_qgemm_i8's
+ * and nqk_qgemm_rows' K-padded left operand as it stands.  Inputs are finite: what a NaN or an
+ * infinity in x gives is unspecified.  The activation is read from HBM once for rows of up to
+ * 4096 columns (a wave keeps its row in registers); longer rows are read twice, the second time
+ * from L2.  Refused before any launch: bit_width outside 2..8, rows < 0, cols <= 0, ldx < cols,
+ * ldq < cols or no multiple of 16, NULL or misaligned pointers (x, s, z 4 bytes; q 16), more than
+ * 2^31 - 1 rows. */
+int nqk_quantize_rows(const float* x, int8_t* q, float* s, int32_t* z, int64_t rows, int64_t cols,
+                      int64_t ldx, int64_t ldq, int bit_width);
+/* The product of such an operand with a symmetric weight, dequantized in the GEMM's epilogue.
+ * a [M][lda] int8 with its rows' s [M] and z [M] (nqk_quantize_rows), bt [N][ldb] int8 the
+ * transposed weight, sw [N] float32 its column scales (a scalar scale broadcast by the caller),
+ * colsum [N] int64 = sum_k bt[n][k].  Per output
+ *   P = sum_k a[m][k] bt[n][k]                                   (int32, exact)
+ *   sc = f32(s[m] * sw[n])                                       (a float32 product)
+ *   out[m][n] = f32(f64(P - z[m] colsum[n]) * f64(sc))           (out [M][ldo] float32)
+ * |P - z colsum| <= 255 * 128 * K, which fits int32 for K < 2^16.  No integer [M][N] array is
+ * written.  Refused before any launch: K no positive multiple of 16 or >= 65536, N <= 0, lda / ldb
+ * no multiple of 16 or shorter than K, ldo < N, NULL or misaligned pointers (a, bt 16 bytes;
+ * colsum 8; s, z, sw, out 4), more than 2^31 - 1 tiles.  M <= 0 launches nothing. */
+int nqk_qgemm_rows(const int8_t* a, const int8_t* bt, const float* s, const int32_t* z, const float* sw,
+                   const int64_t* colsum, float* out, int64_t M, int64_t N, int64_t K, int64_t lda,
+                   int64_t ldb, int64_t ldo);
+
 /* ------------------------------------------- float32 GEMM (BLAS-order exact) */
 /* C = A[M][K] . B[K][N] (element strides a_sm/a_sk, b_sk/b_sn).  Every output element is the
  * reference BLAS's summation: K is cut into OpenBLAS level-3 blocks (GEMM_Q=448

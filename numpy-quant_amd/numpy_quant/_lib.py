@@ -111,6 +111,8 @@ SIGNATURES = {
                           ctypes.POINTER(Gemm16Epilogue)],
     "nqk_qgemm_group": [_p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _i],
     "nqk_group_colsum": [_p, _l, _l, _l, _l, _p],
+    "nqk_quantize_rows": [_p, _p, _p, _p, _l, _l, _l, _l, _i],
+    "nqk_qgemm_rows": [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l],
     "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l, _l, _l],
     "nqk_sgemv_t": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_sgemv_small": [_p, _p, _p, _l, _l, _l],

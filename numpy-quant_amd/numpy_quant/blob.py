@@ -92,6 +92,9 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
     if getattr(qmodel, "group_size", None) is not None:
         raise ValueError("blob: a model with group-wise weight scales (group_size) cannot be saved: no blob "
                          "version holds the [G, N] scale arrays yet")
+    if getattr(qmodel, "per_token", False):
+        raise ValueError("blob: a model with per-token activation scales (per_token) cannot be saved: no blob "
+                         "version records the flag yet")
     consts = []
     off = 0
     for v in qmodel.values:

@@ -618,6 +618,86 @@ class GroupProduct:
         return qmatmul_group(self.a, self.bt, self.gsum, self.sg, self.zpa, self.g)
 
 
+# ----------------------------------------------------------------------------- per-token activation scales
+ROWS_MAX_K = 1 << 16  # nqk_qgemm_rows: |P - z colsum| <= 255 * 128 * K must fit int32
+
+
+class RowQuantized:
+    """A float tensor [..., cols] quantized row by row (nqk_quantize_rows): `q` int8 [rows, ldq] with
+    ldq = cols rounded up to 16 and zero pad bytes, `s` float32 [rows] and `z` int32 [rows] the rows'
+    own scales and zero points.  The left operand of nqk_qgemm_rows; nothing else reads it."""
+
+    def __init__(self, q: DeviceArray, s: DeviceArray, z: DeviceArray, shape, bit_width: int):
+        self.q, self.s, self.z, self.shape, self.bit_width = q, s, z, tuple(shape), bit_width
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+
+def quantize_rows(x: DeviceArray, bit_width: int) -> RowQuantized:
+    """Every row of float32 `x` [..., cols] quantized with the asymmetric parameters of its own range
+    clamped to include 0 (include/nqk.h: the arithmetic), in one read of `x`.  Timed as "quantize_rows"."""
+    if not isinstance(x, DeviceArray) or x.dtype != np.float32 or x.ndim < 1 or x.size == 0:
+        raise ValueError("quantize_rows expects a non-empty float32 DeviceArray of at least one dimension")
+    if isinstance(bit_width, bool) or not isinstance(bit_width, (int, np.integer)) or not 2 <= bit_width <= 8:
+        raise ValueError(f"quantize_rows: bit_width must be an integer in 2..8 (got {bit_width!r})")
+    cols = x.shape[-1]
+    rows = x.size // cols
+    ldq = (cols + 15) // 16 * 16
+    q, s, z = DeviceArray((rows, ldq), np.int8), DeviceArray((rows,), np.float32), DeviceArray((rows,), np.int32)
+    t0 = TIMER.begin() if TIMER is not None else None
+    _lib.call("nqk_quantize_rows", x.vp, q.vp, s.vp, z.vp, rows, cols, cols, ldq, int(bit_width))
+    if t0 is not None:
+        TIMER.end("quantize_rows", t0, (0, 4 * rows * cols + rows * ldq + 8 * rows))
+    return RowQuantized(q, s, z, x.shape, int(bit_width))
+
+
+def qmatmul_rows(a: RowQuantized, bt: DeviceArray, colsum: DeviceArray, sw: DeviceArray) -> DeviceArray:
+    """float32 [..., N] of the row-quantized `a` [..., K] times the symmetric weight `bt` [N, Kp]
+    (weight_bt's image, with its int64 `colsum` [N]) whose column scales are `sw` float32 [N]
+    (nqk_qgemm_rows, include/nqk.h: the arithmetic).  Timed as "qgemm_rows"."""
+    if not isinstance(a, RowQuantized) or bt.dtype != np.int8 or bt.ndim != 2:
+        raise ValueError("qmatmul_rows: a RowQuantized operand and an int8 bt [N, K] expected")
+    N, kp = bt.shape
+    M = a.q.shape[0]
+    if a.q.shape[1] != kp or (a.shape[-1] + 15) // 16 * 16 != kp:
+        raise ValueError(f"qmatmul_rows: K of a ({a.shape[-1]}) does not pad to the K of bt ({kp})")
+    if kp >= ROWS_MAX_K:
+        raise ValueError(f"qmatmul_rows: K must stay below {ROWS_MAX_K} (got {kp})")
+    _check_cols(sw, N, "qmatmul_rows")
+    if colsum.dtype != np.int64 or colsum.size != N:
+        raise ValueError(f"qmatmul_rows: colsum must be int64 [{N}]")
+    out = DeviceArray(a.shape[:-1] + (N,), np.float32)
+    t0 = TIMER.begin() if TIMER is not None else None
+    _lib.call("nqk_qgemm_rows", a.q.vp, bt.vp, a.s.vp, a.z.vp, sw.vp, colsum.vp, out.vp, M, N, kp, kp, kp, N)
+    if t0 is not None:
+        TIMER.end("qgemm_rows", t0, (2 * M * N * kp, M * kp + N * kp + 4 * M * N + 8 * M + 12 * N))
+    return out
+
+
+class RowProduct:
+    """A product of a row-quantized activation with a weight that has not been launched: the operands
+    of nqk_qgemm_rows.  GroupProduct's counterpart, with one consumer: `dequantize`.  No integer
+    accumulator exists for it, since the rank-one scale s[m] * sw[n] is applied in the GEMM's epilogue."""
+
+    def __init__(self, a: RowQuantized, bt: DeviceArray, colsum: DeviceArray, sw: DeviceArray):
+        self.a, self.bt, self.colsum, self.sw = a, bt, colsum, sw
+        self.shape = tuple(a.shape[:-1]) + (bt.shape[0],)
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+    def dequantize(self) -> DeviceArray:
+        return qmatmul_rows(self.a, self.bt, self.colsum, self.sw)
+
+
+# products that only dequantize() reads, and operands that only matmul reads: a QTensor on one of
+# these has no integer array (`dev`)
+NO_ACCUMULATOR = (GroupProduct, RowProduct, RowQuantized)
+
+
 # ----------------------------------------------------------------------------- float GEMM
 def sgemm(a: DeviceArray, a_sm, a_sk, b: DeviceArray, b_sk, b_sn, M, N, K, batch=1, bmap=None,
           a_ms=0, b_ms=0, transb=False) -> DeviceArray:

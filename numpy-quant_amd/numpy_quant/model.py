@@ -26,7 +26,7 @@ from .device import DeviceArray, permute, sync
 from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
 from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, group_scales, qconv2d, quantize_tensor,
-                     where)
+                     quantize_tensor_rows, where)
 from . import kernels as K
 
 
@@ -89,8 +89,9 @@ def _is_image_list(array, pre) -> bool:
 def _topk_output(tensor, k: int):
     """(indices [B, k], probabilities [B, k]) device tensors of a model output [..., classes],
     leading axes flattened into B.  A QTensor is read as it is: no float logits are made (but for a
-    product with group-wise weight scales, which only its dequantize() reads)."""
-    if isinstance(tensor, QTensor) and isinstance(tensor._unlaunched, K.GroupProduct):
+    product with group-wise weight scales or per-token activation scales, which only its
+    dequantize() reads)."""
+    if isinstance(tensor, QTensor) and isinstance(tensor._unlaunched, (K.GroupProduct, K.RowProduct)):
         tensor = tensor.dequantize()
     if not isinstance(tensor, (FTensor, QTensor)) or tensor.dev.ndim < 2:
         shape = tuple(tensor.dev.shape) if hasattr(tensor, "dev") else np.shape(getattr(tensor, "data", None))
@@ -283,6 +284,25 @@ def check_group_args(group_size, bit_width, weight_clip):
     if weight_clip is not None:
         raise ValueError("group_size does not combine with weight_clip: the clipping search is per tensor or per column")
     return group_size
+
+
+def per_token_eligible(node) -> bool:
+    """Whether a node of the float model takes per-token activation scales (QModel.per_token): a
+    MatMul whose input 1 is a constant weight with its columns on the last axis (per_channel_axis).
+    A Gemm is not (its bias is quantized with s_x * s_w), nor are the attention products."""
+    return node.op == "MatMul" and len(node.inputs) == 2 and per_channel_axis(node.inputs[1]) == 1
+
+
+def check_per_token_args(per_token, bit_width, group_size) -> bool:
+    """`per_token` as Model.quantize takes it: a bool, set only beside a bit_width of 2..8 (the rows
+    are stored as int8) and no group_size (nqk_qgemm_group takes one activation scale)."""
+    if not isinstance(per_token, (bool, np.bool_)):
+        raise ValueError(f"per_token must be a bool (got {per_token!r})")
+    if per_token and not 2 <= bit_width <= 8:
+        raise ValueError(f"per_token needs a bit_width of 2..8: the rows are quantized to int8 (got {bit_width})")
+    if per_token and group_size is not None:
+        raise ValueError("per_token does not combine with group_size: a grouped product takes one activation scale")
+    return bool(per_token)
 
 
 def column_scales(tensor: FTensor, axis: int, bit_width: int) -> np.ndarray:
@@ -501,7 +521,7 @@ class Model:
         return equalize(self, batches, alpha, emax, pow2)
 
     def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
         (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
@@ -515,10 +535,16 @@ class Model:
         `group_size=g` (not the reference's behaviour either; a multiple of 32, bit_width <= 8, no
         weight_clip): every MatMul weight [K, N] with K a multiple of g gets one scale per group of
         g consecutive k and column, at the weights' width (QModel.group_size); its products run
-        nqk_qgemm_group.  Every other weight follows the other flags."""
+        nqk_qgemm_group.  Every other weight follows the other flags.
+        `per_token=True` (not the reference's behaviour either; bit_width <= 8, no group_size): the
+        float input of every MatMul with a constant weight (per_token_eligible) is quantized row by
+        row, each token with the scale and zero point of its own range (QModel.per_token); those
+        products run nqk_qgemm_rows.  Gemm nodes and the attention products keep their calibrated
+        scalars."""
         # refused before the calibration forward
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
         check_group_args(group_size, bit_width, weight_clip)
+        check_per_token_args(per_token, bit_width, group_size)
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool, bw=bit_width):
@@ -527,7 +553,7 @@ class Model:
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
                              weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
-                             group_size=group_size)
+                             group_size=group_size, per_token=per_token)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -549,14 +575,17 @@ class Model:
         return cal.ranges()
 
     def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
-                        per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
+                        per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None,
+                        per_token=False):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
         `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
         and maxima of the constants.  So is `weight_clip` with `clip_weights`: two clippers of the
         same constants.  `group_size` as `quantize` takes it; the group ranges are the exact minima
-        and maxima of the constants, whatever `clip_weights` says."""
+        and maxima of the constants, whatever `clip_weights` says.  `per_token` as `quantize` takes
+        it: the rows' ranges are taken at run time, whatever `percentile` says."""
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
         check_group_args(group_size, bit_width, weight_clip)
+        check_per_token_args(per_token, bit_width, group_size)
         if weight_clip is not None and clip_weights:
             raise ValueError("quantize_stream: weight_clip searches the scales of the weights; clip_weights does "
                              "not combine with it")
@@ -571,7 +600,7 @@ class Model:
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
                              weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
-                             group_size=group_size)
+                             group_size=group_size, per_token=per_token)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -629,16 +658,17 @@ class Model:
         return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
 
     def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False, per_channel=False,
-                      weight_bit_width=None):
+                      weight_bit_width=None, per_token=False):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
         skipping the calibration forward.  With `per_channel` the entry of an eligible weight
         (per_channel_axis) may hold a float32 scale vector, one entry per output column; every
         entry is taken as it is given.  With `weight_bit_width` the entry of an eligible weight is
-        the scale of that width: the weight is quantized with it at weight_bit_width."""
+        the scale of that width: the weight is quantized with it at weight_bit_width.  `per_token`
+        as `quantize` takes it; the entries of the row-quantized inputs are kept, unused."""
         return self._rewrite(bit_width, lambda value, asym, bw=None: quant_params[value.name],
                              integer_conv=integer_conv, per_channel=per_channel, given=True,
-                             weight_bit_width=weight_bit_width)
+                             weight_bit_width=weight_bit_width, per_token=per_token)
 
     def load_quantized(self, path):
         """The QModel saved by `QModel.save(path)` (blob.py) on this model's graph:
@@ -647,7 +677,7 @@ class Model:
         return blob.load(self, path)
 
     def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here.
         `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
@@ -660,10 +690,13 @@ class Model:
         through the clipping search (searched_scale) with `clip_steps` candidates; given scales are
         taken as they are.
         `group_size`: eligible MatMul weights (group_eligible) get the scales [K / g, N] of their
-        groups (tensor.group_scales) at the weights' width, whatever `per_channel` says."""
+        groups (tensor.group_scales) at the weights' width, whatever `per_channel` says.
+        `per_token`: the eligible MatMul nodes (per_token_eligible) are recorded; the node loop
+        quantizes their float input row by row.  Every quant_params entry is made as without it."""
         wbw = weight_width(bit_width, weight_bit_width)
         ratios = clip_candidates(weight_clip, clip_steps, wbw)
         group_size = check_group_args(group_size, bit_width, weight_clip)
+        per_token = check_per_token_args(per_token, bit_width, group_size)
         constants = constants or {}
         wanted = {}
         if constants:
@@ -793,6 +826,9 @@ class Model:
         qmodel.weight_bit_width = wbw
         qmodel.weight_clip = weight_clip
         qmodel.group_size = group_size
+        qmodel.per_token = per_token
+        if per_token:
+            qmodel._row_nodes = {node.name for node in self.nodes if per_token_eligible(node)}
         return qmodel
 
 
@@ -837,6 +873,14 @@ class QModel(Model):
         # nqk_qgemm_group's float32 results (tensor.QTensor on a K.GroupProduct), which have no integer
         # accumulator.  Such a model runs the node loop: the plan claims none of its layers.
         self.group_size = None
+        # opt-in, not the reference's behaviour: set by Model.quantize(per_token=True).  The float
+        # input of every MatMul named in _row_nodes (per_token_eligible: a constant weight on input
+        # 1) is quantized row by row with the parameters of each row's own range (nqk_quantize_rows)
+        # instead of its calibrated entry of quant_params, which stays there unused; the product is
+        # nqk_qgemm_rows' float32 result (tensor.QTensor on a K.RowProduct).  Such a model runs the
+        # node loop: the plan claims none of its layers.
+        self.per_token = False
+        self._row_nodes = frozenset()
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "
@@ -994,11 +1038,14 @@ class QModel(Model):
         if self.integer_conv and node.op == "Conv" and integer_conv_eligible(node):
             return self._run_qconv(node, times, profile)
         if node.op in ("MatMul", "Gemm"):
-            for i in node.inputs:
+            for k, i in enumerate(node.inputs):
                 if isinstance(i.data, FTensor):
                     qp = self.quant_params[i.name]
                     t0 = time()
-                    args.append(quantize_tensor(i.data, self.bit_width, qp.scale, qp.zero_point))
+                    if k == 0 and node.name in self._row_nodes:
+                        args.append(quantize_tensor_rows(i.data, self.bit_width))
+                    else:
+                        args.append(quantize_tensor(i.data, self.bit_width, qp.scale, qp.zero_point))
                     if profile:
                         sync()
                     if times is not None:

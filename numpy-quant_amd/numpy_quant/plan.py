@@ -1267,8 +1267,10 @@ class Plan:
             claimed[lg.ln] = claimed[lg.g] = lg
             self.pushdowns += 1
         # group-wise weight scales (QModel.group_size): the fused GEMMs scale once per column, so
-        # such a model's layers stay in the node loop (nqk_qgemm_group)
-        if qmodel.bit_width <= 8 and qmodel.bit_width >= 2 and getattr(qmodel, "group_size", None) is None:
+        # such a model's layers stay in the node loop (nqk_qgemm_group); so do those of a model with
+        # per-token activation scales (QModel.per_token): the fused GEMMs take one activation scale
+        if (qmodel.bit_width <= 8 and qmodel.bit_width >= 2 and getattr(qmodel, "group_size", None) is None
+                and not getattr(qmodel, "per_token", False)):
             for node in qmodel.nodes:
                 if node.op != "LayerNormalization" or node in claimed:
                     continue

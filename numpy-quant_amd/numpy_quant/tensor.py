@@ -244,13 +244,18 @@ class QTensor:
     scale per group of `group_size` = K / G consecutive k and column, no zero point.  `x.matmul(w)`
     of such a weight is a QTensor on a `K.GroupProduct` whose scale is f32(s_x * scale): only
     `dequantize()` reads it (nqk_qgemm_group rescales every group inside its k loop), and whatever
-    needs the integer accumulator raises ValueError."""
+    needs the integer accumulator raises ValueError.
+
+    A QTensor on a `K.RowQuantized` (quantize_tensor_rows, QModel.per_token) is a float tensor
+    quantized row by row: the rows' scales and zero points live on the device, `scale` is None.  It
+    is transient, the left operand of one `matmul` with a constant weight, whose result is a QTensor
+    on a `K.RowProduct` (nqk_qgemm_rows): as with a GroupProduct, only `dequantize()` reads it."""
 
     def __init__(self, data: Union[np.ndarray, DeviceArray], bit_width: int, scale: np.float32,
                  zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None, scale_axis: int = -1):
         self._pending = None  # the K.PendingProduct `dev` is made from on its first read
         self._deq = None  # the FTensor of a pending product's fused dequantize (a value with two consumers)
-        if isinstance(data, (K.PendingProduct, K.GroupProduct)):
+        if isinstance(data, (K.PendingProduct,) + K.NO_ACCUMULATOR):
             self._dev, self._pending = None, data
         elif isinstance(data, DeviceArray):
             if data.dtype.kind != "i":
@@ -307,6 +312,12 @@ class QTensor:
         self._bt16 = None  # the same of a constant int16 weight (nqk_qgemm_i16's operand)
 
     def _needs_accumulator(self, what: str) -> None:
+        if isinstance(self._pending, K.RowQuantized):
+            raise ValueError(f"{what}: a row-quantized tensor (per_token) has one scale and zero point per row, on "
+                             "the device; only matmul with a weight reads it")
+        if isinstance(self._pending, K.RowProduct):
+            raise ValueError(f"{what}: a product of a row-quantized activation has no integer accumulator (the rows' "
+                             "scales are applied inside the GEMM); only dequantize() reads it")
         if isinstance(self._pending, K.GroupProduct):
             raise ValueError(f"{what}: a product with group-wise weight scales has no integer accumulator (every "
                              "group is rescaled inside the GEMM); only dequantize() reads it")
@@ -427,7 +438,9 @@ class QTensor:
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
         pend = self._unlaunched
-        if isinstance(pend, K.GroupProduct):
+        if isinstance(pend, K.RowQuantized):
+            self._needs_accumulator("dequantize")
+        if isinstance(pend, (K.GroupProduct, K.RowProduct)):
             if self._deq is None:
                 self._deq = FTensor(pend.dequantize())
             return self._deq
@@ -504,6 +517,28 @@ class QTensor:
         prod = K.GroupProduct(self.dev, bt, gsum, hit[1], self.zp_scalar, other.group_size)
         return QTensor(prod, 4 * self.bit_width, hit[0], None)
 
+    def _matmul_rows(self, other: "QTensor"):
+        """self, row-quantized [.., K], times a symmetric int8 weight [K, N]: the operands of
+        nqk_qgemm_rows.  sw is the weight's column vector, a scalar scale broadcast to [N] once."""
+        if other.group_size is not None:
+            raise ValueError("matmul: a row-quantized activation (per_token) does not combine with group-wise "
+                             "weight scales")
+        if (not getattr(other, "_is_weight", False) or isinstance(other._pending, K.NO_ACCUMULATOR)
+                or other.dev.ndim != 2 or other.dev.dtype != np.int8 or other._zero_point is not None
+                or other._bias is not None or (other._pc is not None and other.scale_axis != -1)):
+            raise ValueError("matmul: a row-quantized activation (per_token) multiplies a constant 2-D int8 weight "
+                             "without a zero point, its scale a scalar or a vector on its last axis")
+        if other.dev.shape[0] != self.shape[-1]:
+            raise ValueError(f"matmul: mismatch in core dimension ({self.shape[-1]} vs {other.dev.shape[0]})")
+        bt, col = other.weight_operand()
+        if other._pc is not None:
+            sw = other.scale_dev
+        else:
+            sw = getattr(other, "_row_sw", None)
+            if sw is None:
+                sw = other._row_sw = DeviceArray.from_host(np.full(other.dev.shape[1], other.scale, dtype=np.float32))
+        return QTensor(K.RowProduct(self._pending, bt, col, sw), 4 * self.bit_width, None, None)
+
     def weight_operand(self):
         """(Bt, colsum) of a constant int8 or int16 weight, computed once."""
         if self.dev.dtype == np.int16:
@@ -520,6 +555,10 @@ class QTensor:
         narrow_w = ((getattr(other, "_is_weight", False) or getattr(other, "_of_weight", False))
                     and other.bit_width <= self.bit_width)
         assert narrow_w or self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
+        if isinstance(other._pending, K.RowQuantized):
+            raise ValueError("matmul: a row-quantized tensor (per_token) is the left operand only")
+        if isinstance(self._pending, K.RowQuantized):
+            return self._matmul_rows(other)
         if other.group_size is not None:
             return self._matmul_group(other)
         bt = col = None
@@ -598,6 +637,12 @@ def group_scales(tensor: "FTensor", g: int, bit_width: int) -> np.ndarray:
     lo, hi = np.minimum(mn, zero), np.maximum(mx, zero)
     qlo, qhi = -(2.0 ** (bit_width - 1)), 2.0 ** (bit_width - 1) - 1.0
     return ((2 * np.maximum(hi, lo)) / (qhi - qlo)).astype(np.float32).reshape(k // g, n)
+
+
+def quantize_tensor_rows(tensor: FTensor, bit_width: int) -> QTensor:
+    """`tensor` [..., K] quantized row by row with the asymmetric parameters of every row's own range
+    (nqk_quantize_rows; QModel.per_token): a transient QTensor on a K.RowQuantized."""
+    return QTensor(K.quantize_rows(tensor.dev, bit_width), bit_width, None, None)
 
 
 def quantize_tensor(tensor: FTensor, bit_width: int, scale: np.float32, zero_point, scale_axis: int = -1):
