@@ -50,6 +50,68 @@ def test_saturating_operands():
     assert _same(_run(a, b, sg, 127, 256), want)
 
 
+@pytest.mark.parametrize("M,N,g", [(40, 48, 16384), (130, 131, 4096)])
+def test_partial_sums_beyond_float32(M, N, g):
+    """|P_j| just below 255 * 128 * g, 2^29 at the largest g the entry takes: nearly no P_j has a
+    float32 image (tests/test_group_host.py asserts it), so a conversion or a multiply through
+    float32 changes about a quarter of the outputs."""
+    a, b, sg = R.near_limit_operands(M, N, g)
+    assert _same(_run(a, b, sg, 127, g), R.group_matmul(a, b, sg, 127, g))
+
+
+@pytest.mark.parametrize("zpa", [None, 5])
+def test_subnormal_and_overflowing_scales(zpa):
+    a, b, _ = R.operands(33, 48, 96, 32)
+    sg = R.extreme_scale_rows(48)
+    with np.errstate(over="ignore", under="ignore"):
+        want = R.group_matmul(a, b, sg, zpa, 32)
+    assert np.isinf(want).any() and ((want != 0) & (np.abs(want) < np.finfo(np.float32).tiny)).any()
+    assert _same(_run(a, b, sg, zpa, 32), want)
+
+
+@pytest.mark.parametrize("zpa", R.ZPS)
+@pytest.mark.parametrize("M,N,K,g", [(130, 131, 288, 96), (33, 48, 320, 160)])
+def test_groups_of_an_odd_number_of_k_steps(M, N, K, g, zpa):
+    """g / 32 odd: the group boundaries fall alternately in the middle and at the end of a 64-wide k-tile."""
+    a, b, sg = R.operands(M, N, K, g)
+    assert _same(_run(a, b, sg, zpa, g), R.group_matmul(a, b, sg, zpa, g))
+
+
+@pytest.mark.parametrize("zpa", [None, 127])
+def test_64_groups_are_added_in_order(zpa):
+    """Operands whose float32 result depends on the order of the f64 additions (tests/test_group_host.py)."""
+    a, b, sg = R.many_group_operands(70, 136)
+    assert _same(_run(a, b, sg, zpa, 32), R.group_matmul(a, b, sg, zpa, 32))
+
+
+def test_leading_dimensions_and_sentinels():
+    from numpy_quant import _lib
+    M, N, K, g, lda, ldb, ldo, zpa = 130, 131, 192, 96, 208, 224, 136, 5
+    a, b, sg = R.operands(M, N, K, g)
+    ap, btp = np.full((M, lda), 77, np.int8), np.full((N, ldb), 77, np.int8)
+    ap[:, :K], btp[:, :K] = a, b.T
+    G = K // g
+    ad, btd, sgd = _dev(ap), _dev(btp), _dev(sg)
+    gsum, out = _dev(np.full(G * N + 64, -9, np.int32)), _dev(np.full((M, ldo), -7.5, np.float32))
+    _lib.call("nqk_group_colsum", btd.vp, N, K, ldb, g, gsum.vp)
+    gs = gsum.to_host()
+    assert np.array_equal(gs[:G * N].reshape(G, N), b.astype(np.int64).reshape(G, g, N).sum(axis=1)) and np.all(gs[G * N:] == -9)
+    _lib.call("nqk_qgemm_group", ad.vp, btd.vp, sgd.vp, gsum.vp, out.vp, M, N, K, lda, ldb, ldo, g, zpa, 1)
+    got = out.to_host()
+    assert _same(np.ascontiguousarray(got[:, :N]), R.group_matmul(a, b, sg, zpa, g)) and np.all(got[:, N:] == -7.5)
+
+
+def test_group_colsum_grid_stride():
+    """G N = 1 048 640 sums, above the 4096 x 256 threads the launch is capped at: the last 64 are a
+    thread's second trip."""
+    from numpy_quant import kernels as K
+    N, g = 524320, 32
+    bt = np.random.default_rng(3).integers(-128, 128, size=(N, 2 * g), dtype=np.int8)
+    assert 2 * N > 4096 * 256
+    got = K.group_colsum(_dev(bt), g).to_host()
+    assert got.dtype == np.int32 and np.array_equal(got, bt.reshape(N, 2, g).sum(axis=2, dtype=np.int64).T)
+
+
 def test_batch_axis_folds_into_m():
     a, b, sg = R.operands(3 * 50, 80, 128, 32)
     got = _run(a.reshape(3, 50, 128), b, sg, -3, 32)
@@ -78,6 +140,30 @@ def test_entries_refuse_and_launch_nothing(case):
         _lib.call("nqk_qgemm_group", ap, bt.vp, sgd.vp, gsum.vp, out.vp, 32, 32, 96, 96, 96, 32, g, 1, 1)
     with pytest.raises(_lib.NQKError, match="nqk_group_colsum"):
         _lib.call("nqk_group_colsum", bt.ptr + 1 if case == "misaligned" else bt.vp, 32, 96, 96, g, gsum.vp)
+    assert np.all(out.to_host() == 7.0) and np.all(gsum.to_host() == 1)
+
+
+@pytest.mark.parametrize("case", ["g16416", "ldo<N", "lda<K", "zpa128", "gsum null", "sg null", "M0"])
+def test_more_refusals_and_no_rows(case):
+    """Every buffer has the size the refused call names, and M = 0 returns 0; nothing is written."""
+    from numpy_quant import _lib
+    g = 16416 if case == "g16416" else 32
+    M, N, K = 32, 32, 3 * g if g == 32 else g
+    ad, bt = _dev(np.ones((M, K), np.int8)), _dev(np.ones((N, K), np.int8))
+    sgd, gsum = _dev(np.ones((K // g, N), np.float32)), _dev(np.ones((K // g, N), np.int32))
+    out = _dev(np.full((M, N), 7.0, np.float32))
+    kw = dict(sg=sgd.vp, gsum=gsum.vp, M=M, lda=K, ldo=N, zpa=5)
+    kw.update({"g16416": {}, "ldo<N": dict(ldo=N - 1), "lda<K": dict(lda=K - 16), "zpa128": dict(zpa=128),
+               "gsum null": dict(gsum=None), "sg null": dict(sg=None), "M0": dict(M=0)}[case])
+    args = (ad.vp, bt.vp, kw["sg"], kw["gsum"], out.vp, kw["M"], N, K, kw["lda"], K, kw["ldo"], g, kw["zpa"], 1)
+    if case == "M0":
+        _lib.call("nqk_qgemm_group", *args)
+    else:
+        with pytest.raises(_lib.NQKError, match="nqk_qgemm_group"):
+            _lib.call("nqk_qgemm_group", *args)
+    if case == "g16416":
+        with pytest.raises(_lib.NQKError, match="nqk_group_colsum"):
+            _lib.call("nqk_group_colsum", bt.vp, N, K, K, g, gsum.vp)
     assert np.all(out.to_host() == 7.0) and np.all(gsum.to_host() == 1)
 
 
