@@ -314,6 +314,43 @@ int nqk_qgemm_rows(const int8_t* a, const int8_t* bt, const float* s, const int3
                    const int64_t* colsum, float* out, int64_t M, int64_t N, int64_t K, int64_t lda,
                    int64_t ldb, int64_t ldo);
 
+/* OCP Microscaling operands (Model.quantize(mx_format=...)): FP8 or FP4 elements with one
+ * power-of-two scale per block of 32 consecutive k of a row, multiplied on CDNA4's block-scaled
+ * matrix instruction.  Element formats:
+ *   NQK_MXFP8: E4M3, bias 7, subnormals, largest finite value 448 (code 0x7e), no infinity;
+ *              emax_elem = 8; one byte per element
+ *   NQK_MXFP4: E2M1, magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}; emax_elem = 2; two elements per byte,
+ *              even k in the low nibble
+ * A block of finite float32 values v:
+ *   amax = max |v|;  e = max(floor(log2 amax) - emax_elem, -127) from amax's exponent field (a
+ *   subnormal amax gives -127; an all-zero block e = 0);  scale byte = e + 127 (E8M0)
+ *   element = round_to_format(v * 2^-e): to nearest, ties to even, the format's subnormals honoured,
+ *   saturating at the largest finite value; the sign bit of v is kept (also on a zero).
+ * What a NaN or an infinity gives is unspecified.  x [rows][ldx] float32 with cols columns used;
+ * q [rows][ldq] elements (ldq bytes a row at fp8, ldq / 2 at fp4), scales [rows][ldq / 32] bytes.
+ * Columns cols .. ldq - 1 are written as zero elements with scale byte 127: with ldq = cols rounded
+ * up to 128, q and scales are nqk_gemm_mx's K-padded operand as they stand.  x is read once.
+ * Refused before any launch: an unknown format, rows < 0, cols no positive multiple of 32,
+ * ldx < cols, ldq < cols or no multiple of 32, NULL or misaligned pointers (x, q 4 bytes), more
+ * than 2^31 - 1 workgroups. */
+#define NQK_MXFP8 8
+#define NQK_MXFP4 4
+int nqk_quantize_mx(const float* x, uint8_t* q, uint8_t* scales, int64_t rows, int64_t cols, int64_t ldx,
+                    int64_t ldq, int format);
+/* out[m][n] = sum over blocks of 2^(ea + eb) * sum_{k in block} a[m][k] bt[n][k], float32, from
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with the accumulator starting at 0 (the summation order and the
+ * rounding inside the instruction are the hardware's).  a [M][lda] and bt [N][ldb] (the transposed
+ * weight) are elements as nqk_quantize_mx stores them, lda and ldb counted in elements;
+ * a_scales [M][lda / 32] and b_scales [N][ldb / 32].  Format pairs (a, bt): (fp8, fp8), (fp8, fp4),
+ * (fp4, fp4).  The k-step is 128: both operands must hold zero elements and finite scale bytes from
+ * K up to the next multiple of 128.  out [M][ldo].  Refused before any launch: an unknown format or
+ * the pair (fp4, fp8), K no positive multiple of 32, N <= 0, lda / ldb no multiple of 128 or
+ * shorter than K, ldo < N, NULL or misaligned pointers (a, bt 16 bytes; a_scales, b_scales, out 4),
+ * more than 2^31 - 1 tiles.  M <= 0 launches nothing. */
+int nqk_gemm_mx(const uint8_t* a, const uint8_t* a_scales, int a_format, const uint8_t* bt,
+                const uint8_t* b_scales, int b_format, float* out, int64_t M, int64_t N, int64_t K,
+                int64_t lda, int64_t ldb, int64_t ldo);
+
 /* ------------------------------------------- float32 GEMM (BLAS-order exact) */
 /* C = A[M][K] . B[K][N] (element strides a_sm/a_sk, b_sk/b_sn).  Every output element is the
  * reference BLAS's summation: K is cut into OpenBLAS level-3 blocks (GEMM_Q=448

@@ -113,6 +113,8 @@ SIGNATURES = {
     "nqk_group_colsum": [_p, _l, _l, _l, _l, _p],
     "nqk_quantize_rows": [_p, _p, _p, _p, _l, _l, _l, _l, _i],
     "nqk_qgemm_rows": [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l],
+    "nqk_quantize_mx": [_p, _p, _p, _l, _l, _l, _l, _i],
+    "nqk_gemm_mx": [_p, _p, _i, _p, _p, _i, _p, _l, _l, _l, _l, _l, _l],
     "nqk_sgemm": [_p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _l, _lp, _l, _l, _l, _l, _l],
     "nqk_sgemv_t": [_p, _p, _p, _l, _l, _l, _l],
     "nqk_sgemv_small": [_p, _p, _p, _l, _l, _l],

@@ -95,6 +95,9 @@ def pack(qmodel) -> Tuple[dict, DeviceArray]:
     if getattr(qmodel, "per_token", False):
         raise ValueError("blob: a model with per-token activation scales (per_token) cannot be saved: no blob "
                          "version records the flag yet")
+    if getattr(qmodel, "mx_format", None) is not None:
+        raise ValueError("blob: a model with MX operands (mx_format) cannot be saved: no blob version holds the "
+                         "block-scaled weights yet")
     consts = []
     off = 0
     for v in qmodel.values:

@@ -169,14 +169,15 @@ class Comparator:
         if not isinstance(got, (FTensor, QTensor)):
             raise ValueError(f"{name}: the compared side must be an FTensor or a QTensor (got {type(got).__name__})")
         grouped = isinstance(got, QTensor) and (got.group_size is not None or
-                                                isinstance(got._unlaunched, (K.GroupProduct, K.RowProduct)))
+                                                isinstance(got._unlaunched, K.FLOAT_PRODUCTS))
         shape = tuple(got.shape) if isinstance(got, QTensor) else tuple(got.dev.shape)
         if tuple(ref.dev.shape) != shape:
             raise ValueError(f"{name}: shapes differ (float model {tuple(ref.dev.shape)}, quantized model {shape})")
         scale = zp = None
         if isinstance(got, QTensor):
             # group-wise scales: a weight through its own dequantize(), a product through nqk_qgemm_group
-            # (a product of a row-quantized activation, QModel.per_token, through nqk_qgemm_rows)
+            # (a product of a row-quantized activation, QModel.per_token, through nqk_qgemm_rows; a product
+            # of MX operands, QModel.mx_format, through nqk_gemm_mx)
             if grouped or got._bias is not None or isinstance(got._zero_point, K.ZpTerm) or got.per_column:
                 y = got.dequantize().dev  # nqk_compare_stats takes one scalar scale
             else:

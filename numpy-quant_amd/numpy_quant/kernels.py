@@ -693,9 +693,97 @@ class RowProduct:
         return qmatmul_rows(self.a, self.bt, self.colsum, self.sw)
 
 
+# ----------------------------------------------------------------------------- microscaling (MX) operands
+MX_FORMATS = {"mxfp8": 8, "mxfp4": 4}  # name -> bits per element, which is also the C ABI's format code
+MX_PAIRS = (("mxfp8", "mxfp8"), ("mxfp8", "mxfp4"), ("mxfp4", "mxfp4"))  # (activation, weight) as nqk_gemm_mx takes them
+
+
+def check_mx_format(fmt, what="mx format") -> str:
+    if not isinstance(fmt, str) or fmt not in MX_FORMATS:
+        raise ValueError(f"{what} must be one of {sorted(MX_FORMATS)} (got {fmt!r})")
+    return fmt
+
+
+class MxQuantized:
+    """A float tensor [..., cols] in an MX format (nqk_quantize_mx): `q` uint8 [rows, ldq * bits / 8]
+    with ldq = cols rounded up to 128 and zero elements in the padding, `scales` uint8 [rows, ldq / 32],
+    one E8M0 byte per block of 32 consecutive columns.  An operand of nqk_gemm_mx; nothing else reads it."""
+
+    def __init__(self, q: DeviceArray, scales: DeviceArray, fmt: str, shape):
+        self.q, self.scales, self.format, self.shape = q, scales, check_mx_format(fmt), tuple(shape)
+        bits = MX_FORMATS[fmt]
+        ldq = scales.shape[-1] * 32
+        if (q.dtype != np.uint8 or scales.dtype != np.uint8 or q.ndim != 2 or scales.ndim != 2 or ldq % 128
+                or ldq < self.shape[-1] or q.shape != (scales.shape[0], ldq * bits // 8)):
+            raise ValueError(f"MxQuantized: uint8 elements [rows, ldq * {bits} / 8] and scale bytes [rows, ldq / 32] with "
+                             f"ldq a multiple of 128 expected (got {q.shape}, {scales.shape})")
+        self.ldq = ldq
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+
+def quantize_mx(x: DeviceArray, fmt: str) -> MxQuantized:
+    """float32 `x` [..., cols], cols a multiple of 32, in the MX format `fmt`: every block of 32
+    consecutive columns takes the power-of-two scale of its own largest magnitude (include/nqk.h: the
+    rule), in one read of `x`.  Timed as "quantize_mx"."""
+    if not isinstance(x, DeviceArray) or x.dtype != np.float32 or x.ndim < 1 or x.size == 0:
+        raise ValueError("quantize_mx expects a non-empty float32 DeviceArray of at least one dimension")
+    bits = MX_FORMATS[check_mx_format(fmt)]
+    cols = x.shape[-1]
+    if cols % 32:
+        raise ValueError(f"quantize_mx: the last axis must be a multiple of 32 (got {cols})")
+    rows = x.size // cols
+    ldq = (cols + 127) // 128 * 128
+    q, s = DeviceArray((rows, ldq * bits // 8), np.uint8), DeviceArray((rows, ldq // 32), np.uint8)
+    t0 = TIMER.begin() if TIMER is not None else None
+    _lib.call("nqk_quantize_mx", x.vp, q.vp, s.vp, rows, cols, cols, ldq, bits)
+    if t0 is not None:
+        TIMER.end("quantize_mx", t0, (0, 4 * rows * cols + q.nbytes + s.nbytes))
+    return MxQuantized(q, s, fmt, x.shape)
+
+
+def gemm_mx(a: MxQuantized, b: MxQuantized) -> DeviceArray:
+    """float32 [..., N] of the MX operand `a` [..., K] times the MX weight `b`, held transposed [N, K]
+    (nqk_gemm_mx, include/nqk.h: the arithmetic).  Timed as "gemm_mx"."""
+    if not isinstance(a, MxQuantized) or not isinstance(b, MxQuantized) or b.ndim != 2:
+        raise ValueError("gemm_mx: an MxQuantized activation and a 2-D MxQuantized weight [N, K] expected")
+    if (a.format, b.format) not in MX_PAIRS:
+        raise ValueError(f"gemm_mx: the format pair {(a.format, b.format)} is not one of {MX_PAIRS}")
+    N, K = b.shape
+    if a.shape[-1] != K:
+        raise ValueError(f"gemm_mx: mismatch in core dimension ({a.shape[-1]} vs {K})")
+    M = a.q.shape[0]
+    out = DeviceArray(a.shape[:-1] + (N,), np.float32)
+    t0 = TIMER.begin() if TIMER is not None else None
+    _lib.call("nqk_gemm_mx", a.q.vp, a.scales.vp, MX_FORMATS[a.format], b.q.vp, b.scales.vp, MX_FORMATS[b.format],
+              out.vp, M, N, K, a.ldq, b.ldq, N)
+    if t0 is not None:
+        TIMER.end("gemm_mx", t0, (2 * M * N * K, a.q.nbytes + b.q.nbytes + a.scales.nbytes + b.scales.nbytes + 4 * M * N))
+    return out
+
+
+class MxProduct:
+    """A product of two MX operands that has not been launched: RowProduct's counterpart, with one
+    consumer, `dequantize`.  The block scales are applied inside the matrix instruction."""
+
+    def __init__(self, a: MxQuantized, b: MxQuantized):
+        self.a, self.b = a, b
+        self.shape = tuple(a.shape[:-1]) + (b.shape[0],)
+
+    @property
+    def ndim(self) -> int:
+        return len(self.shape)
+
+    def dequantize(self) -> DeviceArray:
+        return gemm_mx(self.a, self.b)
+
+
 # products that only dequantize() reads, and operands that only matmul reads: a QTensor on one of
 # these has no integer array (`dev`)
-NO_ACCUMULATOR = (GroupProduct, RowProduct, RowQuantized)
+FLOAT_PRODUCTS = (GroupProduct, RowProduct, MxProduct)
+NO_ACCUMULATOR = FLOAT_PRODUCTS + (RowQuantized, MxQuantized)
 
 
 # ----------------------------------------------------------------------------- float GEMM

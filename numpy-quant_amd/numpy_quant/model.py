@@ -26,7 +26,7 @@ from .device import DeviceArray, permute, sync
 from .images import QuantLut, UploadSlot
 from .numpy_quantization import quant_parameters
 from .tensor import (FTensor, ITensor, QTensor, Tensor, concat, fconv2d, group_scales, qconv2d, quantize_tensor,
-                     quantize_tensor_rows, where)
+                     quantize_tensor_mx, quantize_tensor_rows, where)
 from . import kernels as K
 
 
@@ -91,7 +91,7 @@ def _topk_output(tensor, k: int):
     leading axes flattened into B.  A QTensor is read as it is: no float logits are made (but for a
     product with group-wise weight scales or per-token activation scales, which only its
     dequantize() reads)."""
-    if isinstance(tensor, QTensor) and isinstance(tensor._unlaunched, (K.GroupProduct, K.RowProduct)):
+    if isinstance(tensor, QTensor) and isinstance(tensor._unlaunched, K.FLOAT_PRODUCTS):
         tensor = tensor.dequantize()
     if not isinstance(tensor, (FTensor, QTensor)) or tensor.dev.ndim < 2:
         shape = tuple(tensor.dev.shape) if hasattr(tensor, "dev") else np.shape(getattr(tensor, "data", None))
@@ -303,6 +303,40 @@ def check_per_token_args(per_token, bit_width, group_size) -> bool:
     if per_token and group_size is not None:
         raise ValueError("per_token does not combine with group_size: a grouped product takes one activation scale")
     return bool(per_token)
+
+
+def mx_eligible(node) -> bool:
+    """Whether a node of the float model takes MX operands (QModel.mx_format): a per_token_eligible
+    MatMul whose K, the weight's first axis, is a multiple of the block size 32."""
+    return per_token_eligible(node) and _const_shape(node.inputs[1])[0] % 32 == 0
+
+
+def _const_shape(value) -> tuple:
+    d = value.data
+    return tuple(d.dev.shape if hasattr(d, "dev") else np.shape(d.data))
+
+
+def check_mx_args(mx_format, mx_weight_format, bit_width, per_token=False, group_size=None, weight_clip=None,
+                  weight_bit_width=None):
+    """(mx_format, mx_weight_format) as Model.quantize takes them: both None, or one of nqk_gemm_mx's
+    pairs of "mxfp8" / "mxfp4" (the weight's format defaults to the activation's), beside a bit_width
+    of at most 8 and none of per_token, group_size, weight_clip and weight_bit_width, which all shape
+    the integer operands that the MX nodes no longer have."""
+    if mx_format is None:
+        if mx_weight_format is not None:
+            raise ValueError("mx_weight_format needs mx_format")
+        return None, None
+    K.check_mx_format(mx_format, "mx_format")
+    wf = mx_format if mx_weight_format is None else K.check_mx_format(mx_weight_format, "mx_weight_format")
+    if (mx_format, wf) not in K.MX_PAIRS:
+        raise ValueError(f"mx_format: the pair (activation, weight) = {(mx_format, wf)} is not one of {K.MX_PAIRS}")
+    if bit_width > 8:
+        raise ValueError(f"mx_format needs a bit_width of at most 8 (got {bit_width})")
+    for name, on in (("per_token", per_token), ("group_size", group_size is not None),
+                     ("weight_clip", weight_clip is not None), ("weight_bit_width", weight_bit_width is not None)):
+        if on:
+            raise ValueError(f"mx_format does not combine with {name}")
+    return mx_format, wf
 
 
 def column_scales(tensor: FTensor, axis: int, bit_width: int) -> np.ndarray:
@@ -521,7 +555,8 @@ class Model:
         return equalize(self, batches, alpha, emax, pow2)
 
     def quantize(self, calibration_inputs: list[np.ndarray], bit_width=8, integer_conv=False, per_channel=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False,
+                 mx_format=None, mx_weight_format=None):
         """Calibration + graph rewrite (model.py:328-442).  `integer_conv=True` (not the
         reference's behaviour): eligible Conv nodes multiply their quantized operands in integers
         (QModel.integer_conv).  `per_channel=True` (not the reference's behaviour either): every
@@ -540,11 +575,18 @@ class Model:
         float input of every MatMul with a constant weight (per_token_eligible) is quantized row by
         row, each token with the scale and zero point of its own range (QModel.per_token); those
         products run nqk_qgemm_rows.  Gemm nodes and the attention products keep their calibrated
-        scalars."""
+        scalars.
+        `mx_format="mxfp8"` or `"mxfp4"` (not the reference's behaviour either; bit_width <= 8, none of
+        per_token, group_size, weight_clip, weight_bit_width): the same MatMuls whose K is a multiple
+        of 32 (mx_eligible) take OCP Microscaling operands: their float input is quantized on arrival
+        and their weight once, in `mx_weight_format` (default: mx_format; ("mxfp4", "mxfp8") is
+        refused), to FP8 or FP4 elements with a power-of-two scale per 32 consecutive k
+        (QModel.mx_format); those products run nqk_gemm_mx.  Everything else follows the other flags."""
         # refused before the calibration forward
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
         check_group_args(group_size, bit_width, weight_clip)
         check_per_token_args(per_token, bit_width, group_size)
+        check_mx_args(mx_format, mx_weight_format, bit_width, per_token, group_size, weight_clip, weight_bit_width)
         vmin, vmax = self.calibrate(calibration_inputs)
 
         def params(value: Value, asym: bool, bw=bit_width):
@@ -553,7 +595,8 @@ class Model:
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
                              weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
-                             group_size=group_size, per_token=per_token)
+                             group_size=group_size, per_token=per_token, mx_format=mx_format,
+                             mx_weight_format=mx_weight_format)
 
     def calibrate_stream(self, batches, percentile=100.0, clip_weights=False) -> tuple[dict, dict]:
         """`calibrate` over any number of batches (calibration.py): per batch one float forward
@@ -576,16 +619,18 @@ class Model:
 
     def quantize_stream(self, batches, bit_width=8, percentile=100.0, clip_weights=False, integer_conv=False,
                         per_channel=False, weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None,
-                        per_token=False):
+                        per_token=False, mx_format=None, mx_weight_format=None):
         """`quantize` with the ranges of `calibrate_stream(batches, percentile, clip_weights)`.
         `per_channel` with `clip_weights` is refused: the per-column ranges are the exact minima
         and maxima of the constants.  So is `weight_clip` with `clip_weights`: two clippers of the
         same constants.  `group_size` as `quantize` takes it; the group ranges are the exact minima
         and maxima of the constants, whatever `clip_weights` says.  `per_token` as `quantize` takes
-        it: the rows' ranges are taken at run time, whatever `percentile` says."""
+        it: the rows' ranges are taken at run time, whatever `percentile` says.  `mx_format` and
+        `mx_weight_format` as `quantize` takes them: the block scales come from the blocks themselves."""
         clip_candidates(weight_clip, clip_steps, weight_width(bit_width, weight_bit_width))
         check_group_args(group_size, bit_width, weight_clip)
         check_per_token_args(per_token, bit_width, group_size)
+        check_mx_args(mx_format, mx_weight_format, bit_width, per_token, group_size, weight_clip, weight_bit_width)
         if weight_clip is not None and clip_weights:
             raise ValueError("quantize_stream: weight_clip searches the scales of the weights; clip_weights does "
                              "not combine with it")
@@ -600,7 +645,8 @@ class Model:
 
         return self._rewrite(bit_width, params, integer_conv=integer_conv, per_channel=per_channel,
                              weight_bit_width=weight_bit_width, weight_clip=weight_clip, clip_steps=clip_steps,
-                             group_size=group_size, per_token=per_token)
+                             group_size=group_size, per_token=per_token, mx_format=mx_format,
+                             mx_weight_format=mx_weight_format)
 
     def compare(self, qmodel, batches, k=5, labels=None, values=True):
         """What `qmodel` lost against this float model over an evaluation set: a
@@ -658,17 +704,20 @@ class Model:
         return Report(cmp.report(states), k, agree, qmodel.bit_width, states)
 
     def quantize_with(self, quant_params: dict, bit_width=8, integer_conv=False, per_channel=False,
-                      weight_bit_width=None, per_token=False):
+                      weight_bit_width=None, per_token=False, mx_format=None, mx_weight_format=None):
         """The graph rewrite of Model.quantize with given per-value quantization
         parameters (e.g. calibrated on a smaller batch, or the reference's own),
         skipping the calibration forward.  With `per_channel` the entry of an eligible weight
         (per_channel_axis) may hold a float32 scale vector, one entry per output column; every
         entry is taken as it is given.  With `weight_bit_width` the entry of an eligible weight is
         the scale of that width: the weight is quantized with it at weight_bit_width.  `per_token`
-        as `quantize` takes it; the entries of the row-quantized inputs are kept, unused."""
+        as `quantize` takes it; the entries of the row-quantized inputs are kept, unused.  So are
+        those of the MX nodes' inputs and weights with `mx_format` / `mx_weight_format`."""
+        check_mx_args(mx_format, mx_weight_format, bit_width, per_token, None, None, weight_bit_width)
         return self._rewrite(bit_width, lambda value, asym, bw=None: quant_params[value.name],
                              integer_conv=integer_conv, per_channel=per_channel, given=True,
-                             weight_bit_width=weight_bit_width, per_token=per_token)
+                             weight_bit_width=weight_bit_width, per_token=per_token, mx_format=mx_format,
+                             mx_weight_format=mx_weight_format)
 
     def load_quantized(self, path):
         """The QModel saved by `QModel.save(path)` (blob.py) on this model's graph:
@@ -677,7 +726,8 @@ class Model:
         return blob.load(self, path)
 
     def _rewrite(self, bit_width, params, constants=None, integer_conv=False, per_channel=False, given=False,
-                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False):
+                 weight_bit_width=None, weight_clip=None, clip_steps=64, group_size=None, per_token=False,
+                 mx_format=None, mx_weight_format=None):
         """model.py:338-442.  `constants`: name -> ready quantized QTensor (blob.py);
         those constants are taken as they are instead of being quantized here.
         `per_channel`: eligible weights (per_channel_axis) get a scale per output column, computed
@@ -692,11 +742,16 @@ class Model:
         `group_size`: eligible MatMul weights (group_eligible) get the scales [K / g, N] of their
         groups (tensor.group_scales) at the weights' width, whatever `per_channel` says.
         `per_token`: the eligible MatMul nodes (per_token_eligible) are recorded; the node loop
-        quantizes their float input row by row.  Every quant_params entry is made as without it."""
+        quantizes their float input row by row.  Every quant_params entry is made as without it.
+        `mx_format`, `mx_weight_format`: the eligible MatMul nodes (mx_eligible) are recorded and their
+        weights get an MX image of the float constant (QTensor.mx_operand) beside the integers, which
+        are made as without it, as is every quant_params entry."""
         wbw = weight_width(bit_width, weight_bit_width)
         ratios = clip_candidates(weight_clip, clip_steps, wbw)
         group_size = check_group_args(group_size, bit_width, weight_clip)
         per_token = check_per_token_args(per_token, bit_width, group_size)
+        mx_format, mx_weight_format = check_mx_args(mx_format, mx_weight_format, bit_width, per_token, group_size,
+                                                    weight_clip, None)
         constants = constants or {}
         wanted = {}
         if constants:
@@ -829,6 +884,14 @@ class Model:
         qmodel.per_token = per_token
         if per_token:
             qmodel._row_nodes = {node.name for node in self.nodes if per_token_eligible(node)}
+        qmodel.mx_format, qmodel.mx_weight_format = mx_format, mx_weight_format
+        if mx_format is not None:
+            if constants:
+                raise ValueError("mx_format: the constants of a blob hold no MX image")
+            mx_nodes = [node for node in self.nodes if mx_eligible(node)]
+            qmodel._mx_nodes = {node.name for node in mx_nodes}
+            for node in mx_nodes:  # the weight, once, from the float constant's transposed view
+                qvalues[node.inputs[1].name].data.mx_operand(mx_weight_format, node.inputs[1].data)
         return qmodel
 
 
@@ -881,6 +944,17 @@ class QModel(Model):
         # node loop: the plan claims none of its layers.
         self.per_token = False
         self._row_nodes = frozenset()
+        # opt-in, not the reference's behaviour: the activations' and the weights' OCP Microscaling
+        # format of Model.quantize(mx_format=..., mx_weight_format=...), "mxfp8" or "mxfp4", else None.
+        # The float input of every MatMul named in _mx_nodes (mx_eligible) is quantized block by block
+        # (nqk_quantize_mx: 32 consecutive k share a power-of-two scale) instead of with its calibrated
+        # entry of quant_params, which stays there unused like the weight's; the weight keeps an MX
+        # image of its float constant, and the product is nqk_gemm_mx's float32 result
+        # (tensor.QTensor on a K.MxProduct).  Such a model runs the node loop: the plan claims none of
+        # its layers.
+        self.mx_format = None
+        self.mx_weight_format = None
+        self._mx_nodes = frozenset()
 
     def __repr__(self):
         return (f"QModel({len(self.nodes)} nodes, {len(self.values)} values, bit_width={self.bit_width}, "
@@ -1044,6 +1118,8 @@ class QModel(Model):
                     t0 = time()
                     if k == 0 and node.name in self._row_nodes:
                         args.append(quantize_tensor_rows(i.data, self.bit_width))
+                    elif k == 0 and node.name in self._mx_nodes:
+                        args.append(quantize_tensor_mx(i.data, self.mx_format))
                     else:
                         args.append(quantize_tensor(i.data, self.bit_width, qp.scale, qp.zero_point))
                     if profile:

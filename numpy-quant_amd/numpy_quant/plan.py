@@ -1268,9 +1268,10 @@ class Plan:
             self.pushdowns += 1
         # group-wise weight scales (QModel.group_size): the fused GEMMs scale once per column, so
         # such a model's layers stay in the node loop (nqk_qgemm_group); so do those of a model with
-        # per-token activation scales (QModel.per_token): the fused GEMMs take one activation scale
+        # per-token activation scales (QModel.per_token): the fused GEMMs take one activation scale; and
+        # those of a model with MX operands (QModel.mx_format): the fused GEMMs are integer
         if (qmodel.bit_width <= 8 and qmodel.bit_width >= 2 and getattr(qmodel, "group_size", None) is None
-                and not getattr(qmodel, "per_token", False)):
+                and not getattr(qmodel, "per_token", False) and getattr(qmodel, "mx_format", None) is None):
             for node in qmodel.nodes:
                 if node.op != "LayerNormalization" or node in claimed:
                     continue

@@ -249,7 +249,13 @@ class QTensor:
     A QTensor on a `K.RowQuantized` (quantize_tensor_rows, QModel.per_token) is a float tensor
     quantized row by row: the rows' scales and zero points live on the device, `scale` is None.  It
     is transient, the left operand of one `matmul` with a constant weight, whose result is a QTensor
-    on a `K.RowProduct` (nqk_qgemm_rows): as with a GroupProduct, only `dequantize()` reads it."""
+    on a `K.RowProduct` (nqk_qgemm_rows): as with a GroupProduct, only `dequantize()` reads it.
+
+    A QTensor on a `K.MxQuantized` (quantize_tensor_mx, QModel.mx_format) is a float tensor in an MX
+    format, FP8 or FP4 elements with one power-of-two scale per block of 32 on the last axis; `scale`
+    is None.  It too is the transient left operand of one `matmul` with a constant 2-D weight that
+    holds an MX image of itself (`mx_operand`); the result is a QTensor on a `K.MxProduct`
+    (nqk_gemm_mx), which only `dequantize()` reads."""
 
     def __init__(self, data: Union[np.ndarray, DeviceArray], bit_width: int, scale: np.float32,
                  zero_point: Optional[Any] = None, bias: Optional["QTensor"] = None, scale_axis: int = -1):
@@ -310,8 +316,15 @@ class QTensor:
         self._bias = bias
         self._bt = None  # cached (Bt, colsum) when this is a constant int8 weight
         self._bt16 = None  # the same of a constant int16 weight (nqk_qgemm_i16's operand)
+        self._mx = None  # the K.MxQuantized [N, K] of the float weight this constant was quantized from (mx_operand)
 
     def _needs_accumulator(self, what: str) -> None:
+        if isinstance(self._pending, K.MxQuantized):
+            raise ValueError(f"{what}: an MX-quantized tensor (mx_format) has one scale per block of 32, on the "
+                             "device; only matmul with a weight reads it")
+        if isinstance(self._pending, K.MxProduct):
+            raise ValueError(f"{what}: a product of MX operands has no integer accumulator (the block scales are "
+                             "applied inside the matrix instruction); only dequantize() reads it")
         if isinstance(self._pending, K.RowQuantized):
             raise ValueError(f"{what}: a row-quantized tensor (per_token) has one scale and zero point per row, on "
                              "the device; only matmul with a weight reads it")
@@ -438,9 +451,9 @@ class QTensor:
         if self._bias is not None:
             raise ValueError("dequantize of a biased Gemm accumulator: requantize it first")
         pend = self._unlaunched
-        if isinstance(pend, K.RowQuantized):
+        if isinstance(pend, (K.RowQuantized, K.MxQuantized)):
             self._needs_accumulator("dequantize")
-        if isinstance(pend, (K.GroupProduct, K.RowProduct)):
+        if isinstance(pend, K.FLOAT_PRODUCTS):
             if self._deq is None:
                 self._deq = FTensor(pend.dequantize())
             return self._deq
@@ -539,6 +552,25 @@ class QTensor:
                 sw = other._row_sw = DeviceArray.from_host(np.full(other.dev.shape[1], other.scale, dtype=np.float32))
         return QTensor(K.RowProduct(self._pending, bt, col, sw), 4 * self.bit_width, None, None)
 
+    def mx_operand(self, fmt: str, source: Optional["FTensor"] = None) -> K.MxQuantized:
+        """The MX image [N, K] of the float weight [K, N] this constant was quantized from, made once
+        per format from `source` (Model._rewrite hands it over) and kept."""
+        if self._mx is None or self._mx.format != fmt:
+            if source is None or source.dev.ndim != 2 or tuple(source.dev.shape) != tuple(self.shape):
+                raise ValueError(f"mx_operand: this weight holds no {fmt!r} image (Model.quantize(mx_format=...) makes "
+                                 "it for a constant 2-D weight)")
+            self._mx = K.quantize_mx(permute(source.dev, [1, 0]), fmt)
+        return self._mx
+
+    def _matmul_mx(self, other: "QTensor"):
+        """self, MX-quantized [.., K], times a constant 2-D weight [K, N] through its MX image."""
+        if not getattr(other, "_is_weight", False) or other._mx is None or len(other.shape) != 2:
+            raise ValueError("matmul: an MX-quantized activation (mx_format) multiplies a constant 2-D weight that "
+                             "holds an MX image")
+        if other.shape[0] != self.shape[-1]:
+            raise ValueError(f"matmul: mismatch in core dimension ({self.shape[-1]} vs {other.shape[0]})")
+        return QTensor(K.MxProduct(self._pending, other._mx), 4 * self.bit_width, None, None)
+
     def weight_operand(self):
         """(Bt, colsum) of a constant int8 or int16 weight, computed once."""
         if self.dev.dtype == np.int16:
@@ -552,6 +584,10 @@ class QTensor:
     def matmul(self, other: "QTensor"):
         # a weight may be narrower than the activation it multiplies (QModel.weight_bit_width):
         # q_matmul is the same integer product; two non-weight operands have one width
+        if isinstance(other._pending, K.MxQuantized):
+            raise ValueError("matmul: an MX-quantized tensor (mx_format) is the left operand only")
+        if isinstance(self._pending, K.MxQuantized):
+            return self._matmul_mx(other)
         narrow_w = ((getattr(other, "_is_weight", False) or getattr(other, "_of_weight", False))
                     and other.bit_width <= self.bit_width)
         assert narrow_w or self.bit_width == other.bit_width, f"{self.bit_width} != {other.bit_width}"
@@ -643,6 +679,12 @@ def quantize_tensor_rows(tensor: FTensor, bit_width: int) -> QTensor:
     """`tensor` [..., K] quantized row by row with the asymmetric parameters of every row's own range
     (nqk_quantize_rows; QModel.per_token): a transient QTensor on a K.RowQuantized."""
     return QTensor(K.quantize_rows(tensor.dev, bit_width), bit_width, None, None)
+
+
+def quantize_tensor_mx(tensor: FTensor, fmt: str) -> QTensor:
+    """`tensor` [..., K], K a multiple of 32, in the MX format `fmt` ("mxfp8" or "mxfp4"; nqk_quantize_mx,
+    QModel.mx_format): a transient QTensor on a K.MxQuantized."""
+    return QTensor(K.quantize_mx(tensor.dev, fmt), K.MX_FORMATS[K.check_mx_format(fmt)], None, None)
 
 
 def quantize_tensor(tensor: FTensor, bit_width: int, scale: np.float32, zero_point, scale_axis: int = -1):
